@@ -5,8 +5,13 @@
     python bench.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  `value` / `ms_per_step` come from EXACTLY K steps of the clean
-product path; a second block of instrumented steps right after it feeds
+Prints ONE JSON line on rank 0.  `value` / `ms_per_step` come from EXACTLY K steps of the clean product path.  A plain run does only
+what that figure needs: set-up, settle steps, W warm-up steps, the K timed steps, the line.
+  --dump-outputs DIR : after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (dump_train_outputs,
+                       dump_inference_outputs); inputs and the steps before the last one are the same from run to run, so two builds
+                       can be compared output for output.
+  --full             : also the measurements below (its --no-* flag still switches each one off).
+With --full, a second block of instrumented steps right after the timed ones feeds
   roofline     : the dominant kernel family = the fp16-plane gather-GEMM (conv_pl.hip: implicit-GEMM conv fwd + dgrad, f16x3 split
                  arithmetic); achieved = algorithmic fp32 FLOPs (2*M*N*K with all taps counted) / its launch time
                  measured live with HIP events on the launch stream; peak = dense 16-bit MFMA
@@ -14,8 +19,10 @@ product path; a second block of instrumented steps right after it feeds
   roofline.hbm : the HBM-bound family = the BatchNorm passes (bn.hip): algorithmic bytes per step / HIP-event time vs 8 TB/s.
   cpu_baseline : the CPU oracle (a restatement pinned bit-exactly to the reference) timed on the host cores on a
                  bounded sample of the same workload (rank 0, N=1 only).
+  config.dp_codepath_overhead : N=1, the same steps with a one-rank RCCL group switched on.
 """
 import argparse
+import gc
 import json
 import os
 import sys
@@ -56,6 +63,61 @@ def synth(rank, b, ch, hw, n_cls, dev):
     x = torch.from_numpy(np.random.RandomState(1234 + rank).randint(0, 256, (b, ch, hw, hw)).astype(np.float32)).to(dev)
     y = torch.from_numpy(np.random.RandomState(4321 + rank).randint(0, n_cls, (b, hw, hw)).astype(np.int64)).to(dev)
     return x, y
+
+
+DUMP_SAMPLE = 16384               # --dump-outputs: elements kept per tensor (all of a smaller one)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample_index(name, n):
+    """Fixed, seeded sample of min(n, DUMP_SAMPLE) flat indices of an n-element tensor: one index drawn in each of k equal strata, the
+    draws seeded by the tensor's name (a tensor's sample does not depend on which other tensors exist)."""
+    import zlib
+    k = min(n, DUMP_SAMPLE)
+    lo = np.arange(k, dtype=np.int64) * n // k
+    hi = np.arange(1, k + 1, dtype=np.int64) * n // k
+    return lo + (np.random.RandomState(zlib.crc32(name.encode())).random_sample(k) * (hi - lo)).astype(np.int64)
+
+
+def _sampled(named):
+    """fp32 concatenation of the samples of the floating-point tensors in `named` ([(name, tensor)], in that order), each taken in the
+    tensor's logical (shape) order, whatever its memory layout."""
+    parts = []
+    for name, t in named:
+        if t is None or not t.is_floating_point():
+            continue
+        flat = t.detach().reshape(-1)
+        parts.append(flat[torch.from_numpy(_sample_index(name, flat.numel())).to(flat.device)].float())
+    return torch.cat(parts).cpu().numpy()
+
+
+def _write_dump(out_dir, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes, more than the %d allowed' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def dump_train_outputs(model, loss, out_dir):
+    """What the caller of Model.train holds after the last timed step: the returned loss, its three terms (ce, dice, focal), and the
+    updated network -- parameters, their gradients (p.grad) and the BatchNorm running statistics, a fixed sample of each tensor."""
+    net = model.net
+    params = list(net.named_parameters())
+    _write_dump(out_dir, {
+        'loss': loss.detach().double().reshape(1).cpu().numpy(),
+        'loss_terms': torch.stack((model.crit.ce, model.crit.dsc, model.crit.fl)).detach().double().reshape(3).cpu().numpy(),
+        'params': _sampled(params),
+        'grads': _sampled([(n, p.grad) for n, p in params]),
+        'buffers': _sampled(list(net.named_buffers())),
+    })
+
+
+def dump_inference_outputs(mask, out_dir):
+    """The class mask predict_image returned for the last timed image (3072 x 4096, whole)."""
+    _write_dump(out_dir, {'mask': mask.float().cpu().numpy()})
 
 
 def _side_stream_on():
@@ -214,6 +276,8 @@ def inference_leg(args, cfg, model, rank, world, dev):
     model.net.eval()
     for _ in range(max(args.warmup, 2)):
         inference.predict_image(model, img, tile, stride, batch, group=group)
+    from pylc_amd import ops as _ops
+    _ops.eval_plane_convs[0] = 0
     parallel.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -222,11 +286,10 @@ def inference_leg(args, cfg, model, rank, world, dev):
     parallel.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    from pylc_amd import ops as _ops
-    _ops.eval_plane_convs[0] = 0
-    inference.predict_image(model, img, tile, stride, batch, group=group)
-    plane_convs = _ops.eval_plane_convs[0]
-    # roofline leg: one more image with HIP events around the fused conv + BatchNorm launches (after the timed region)
+    plane_convs = _ops.eval_plane_convs[0] // args.steps
+    if args.dump_outputs and rank == 0:
+        dump_inference_outputs(mask, args.dump_outputs)
+    # roofline leg (--full): one more image with HIP events around the fused conv + BatchNorm launches (after the timed region)
     roof = None
     if not args.no_kernel_timing:
         from pylc_amd import ops
@@ -290,7 +353,14 @@ def main():
     ap.add_argument('--config', default='c3', choices=sorted(CONFIGS), help='BASELINE.json configuration (default c3 = configs[2], the headline)')
     ap.add_argument('--inference', action='store_true', help='with --config c5: the inference leg of configs[4] -- sliding-window prediction of a '
                     'synthetic full-resolution 3072x4096 image (1024^2 tiles, stride 512, batches of 8: test.py:50-110); a step = one image')
+    ap.add_argument('--full', action='store_true', help='also the measurements beyond the headline: the instrumented roofline block, the N=1 '
+                    'data-parallel code-path leg and the CPU baseline (each still off with its --no-* flag)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (float32 / float64)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:            # a plain run: set-up, settle, warm-up, the timed steps, the line
+        args.no_kernel_timing = args.no_dp_overhead = args.no_cpu_baseline = True
     cfg = CONFIGS[args.config]
     if args.config != 'c3':
         args.batch, args.tile, args.classes = cfg['batch'], cfg['tile'], cfg['classes']
@@ -337,8 +407,18 @@ def main():
             done = flag.item() == 0.0
         if done:
             break
+    # The settle ran a timing-dependent number of optimiser steps.  The warm-up and timed steps get a fresh model built from the same
+    # seeds, its memory out of the pool the settled one hands back, so that the state entering them -- and with it what --dump-outputs
+    # writes -- is the same from run to run.
+    del model
+    gc.collect()          # (now, not inside the timed region)
+    torch.manual_seed(0)
+    pylc_amd.runtime.manual_seed(0, rank)           # the dropout seeds restart as well
+    model = Model(meta, dev).build()
+    if world > 1:
+        parallel.broadcast_parameters(model.arena)
     for _ in range(args.warmup):
-        model.train(x, y)
+        loss = model.train(x, y)      # (held as in the timed loop)
     ops.amax_passes[:] = [0, 0]
     ops.plane_conversions[:] = [0, 0]
     ops.planes_marked[0] = 0
@@ -350,11 +430,13 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        model.train(x, y)
+        loss = model.train(x, y)
     parallel.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     mallocs = torch.cuda.memory_stats().get('num_device_alloc', 0) - mallocs
+    if args.dump_outputs and rank == 0:
+        dump_train_outputs(model, loss, args.dump_outputs)
     clean_collectives = pylc_amd.runtime.collectives
     range_passes, conversions = ops.amax_passes[0] / args.steps, ops.plane_conversions[0] / args.steps
     planes_marked = ops.planes_marked[0] / args.steps

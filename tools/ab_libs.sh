@@ -5,6 +5,7 @@
 set -o pipefail
 tag=$1; shift
 rounds=${ROUNDS:-2}
+BENCH_ARGS="--full $BENCH_ARGS"      # roofline.by_kind / roofline.hbm come from the instrumented block
 mkdir -p gpurun_out/$tag
 for r in $(seq 1 $rounds); do
   for lib in "$@"; do

@@ -5,6 +5,7 @@
 # e.g.   bash tools/ab_multi.sh 2 "" "PYLC_RUNTIME=no_relu_bits=1"          BENCH_ARGS="--config c5" bash tools/ab_multi.sh 2 "PYLC_RUNTIME=half_acts=0" ""
 set -o pipefail
 rounds=$1; shift
+BENCH_ARGS="--full $BENCH_ARGS"      # the line printed per run reads the roofline block
 mkdir -p gpurun_out/ab_multi
 for i in $(seq 1 $rounds); do
   k=0
