@@ -35,7 +35,7 @@ extern "C" {
 #define PYLC_ERR_UNSUPPORTED 4   /* an optional run-time dependency is absent (pylc_comm_*: no loadable librccl) */
 
 const char* pylc_last_error(void);
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header (bumped on any signature change): 14 (pylc_image_pack_tiles_reflect, pylc_stitch_overlap_argmax). */
 int pylc_abi_version(void);
 /* 1 when the library was built with EXPERIMENTAL=1, i.e. the entry points inside #ifdef PYLC_EXPERIMENTAL below exist (pylc_amd/csrc/Makefile) */
 int pylc_experimental_build(void);
@@ -558,6 +558,26 @@ int pylc_stitch_argmax(const float* logits, int pitch, int rows, int cols, int t
 /* out_rgb[oy][ox][3] = palette[mask[floor(oy*h/oh)][floor(ox*w/ow)]]; palette_rgb: device uint8 [n_classes][3]. */
 int pylc_colourize_resize(const unsigned char* mask, int h, int w, const unsigned char* palette_rgb,
                           unsigned char* out_rgb, int oh, int ow, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * Full-image U-Net inference by overlap tiles (ABI 14, csrc/overlap_tile.hip): the mirror-padded geometry the
+ * reference records in config.py:225-236 (input_size 512, output_size 324) and test.py:50-110 cannot run, since
+ * utils/tools.py:209-319 reconstruct() assumes same-size tiles.  With pad = (tile - out) / 2, the output-tile
+ * origins along an axis of length H are o_i = min(i*stride, H - out), i = 0 .. ceil((H - out) / stride); tile
+ * (i, j) reads [o_i - pad, o_i + out + pad) x [o_j - pad, o_j + out + pad) of the image mirrored at its edges
+ * (reflect-101, torch.nn.functional.pad mode='reflect').  Requires 1 <= stride <= out, H, W >= out, pad < H, W.
+ * ------------------------------------------------------------------------------------------- */
+/* img: [Cimg][H][W] raw 0..255, float32 (is_u8 = 0) or uint8 (is_u8 = 1), any H, W meeting the above; writes tiles
+ * first_tile .. first_tile+n_tiles-1 (row-major tile order) as [n][tile][tile][4] with pylc_image_pack_tiles'
+ * arithmetic, ((v - mean) / std) / 255, channel 3 = 0, one image channel copied into three.  mean3/std3: HOST arrays. */
+int pylc_image_pack_tiles_reflect(const void* img, int is_u8, int Cimg, int H, int W, int tile, int out, int stride,
+                                  int first_tile, int n_tiles, const float* mean3, const float* std3, float* tiles,
+                                  void* stream);
+/* logits: [n_tiles][out][out][pitch] (NHWC tiles in row-major tile order, pitch >= C and a multiple of 4, 16-B aligned),
+ * n_tiles = the grid's rows*cols.  Every pixel takes the mean of the softmax probabilities of the tiles covering it
+ * (equal weights, tile rows ascending then columns: deterministic) and mask[H][W] (uint8) its argmax (first maximum).
+ * probs: NULL, or fp32 [C][H][W] receiving those means (the layout of the reference's mask_fullsized). C in 2..16. */
+int pylc_stitch_overlap_argmax(const float* logits, int pitch, int n_tiles, int H, int W, int out, int stride, int C,
+                               unsigned char* mask, float* probs, void* stream);
 
 /* Confusion matrix cm[t*C + p] += 1 over n pixels of class-index masks (uint8 or int64; *_bytes = 1 or 8); the scores of
  * utils/metrics.py:64-88 (weighted F1, weighted IoU = the "mIoU", MCC, normalised matrix) are functions of it.

@@ -1,0 +1,220 @@
+// Full-image U-Net inference by the overlap-tile method (U-Net paper, section 3; the geometry the reference records in
+// config.py:225-236 -- input_size 512, output_size 324, the image padded by mirroring -- but never wires up: utils/tools.py:209-319
+// reconstruct() assumes same-size tiles).  A valid-convolution U-Net maps a `tile` window to the centred `out = tile - 2*pad`
+// square, so:
+//
+//   output-tile origins along an axis of length H:  o_i = min(i*stride, H - out),  i = 0 .. ceil((H - out) / stride)
+//   tile (i, j) reads the window [o_i - pad, o_i + out + pad) x [o_j - pad, o_j + out + pad) of the image mirrored at its edges
+//   (reflect-101: the edge pixel is not repeated, torch.nn.functional.pad(mode='reflect')); the clamped last tile keeps every
+//   window within `pad` of the image, so one reflection suffices (pad < H, pad < W)
+//   score of an image pixel = mean of the softmax probabilities of every tile that covers it (equal weights, summed in tile order:
+//   rows ascending, then columns -- no atomics, deterministic); class = argmax, first maximum
+//
+// pack_tiles_reflect_kernel cuts and normalises the windows straight from the device image (float or uint8); stitch_overlap_kernel
+// reads each pixel's covering logit tiles (<= ceil(out/stride)+1 per axis) and writes the uint8 mask, optionally the mean
+// probabilities [C][H][W] (the reference's mask_fullsized layout).
+#include <type_traits>
+
+#include "common.h"
+
+namespace pylc {
+
+namespace {
+
+typedef float ot_f32x4 __attribute__((ext_vector_type(4)));
+
+struct OverlapGeom { int H, W, out, stride, rows, cols, pitch; };
+
+// number of output-tile origins along an axis of length n (n >= out)
+__host__ __device__ inline int overlap_count(int n, int out, int stride) { return (n - out + stride - 1) / stride + 1; }
+
+// origin of tile i along an axis of length n
+__device__ __forceinline__ int overlap_origin(int i, int n, int out, int stride) {
+    const int o = i * stride;
+    return o < n - out ? o : n - out;
+}
+
+// tiles covering coordinate y along an axis: the unclamped tiles lo .. hi (origin i*stride), then the clamped last tile cnt-1 when
+// y >= n - out.  Visited as a = lo .. hi + last, tile = a <= hi ? a : cnt - 1 (ascending either way; lo <= hi + 1 always).
+struct Cover { int lo, hi, last; };
+__device__ __forceinline__ Cover overlap_cover(int y, int n, int out, int stride, int cnt) {
+    Cover c;
+    c.lo = y < out ? 0 : (y - out) / stride + 1;
+    const int h = y / stride;
+    c.hi = h < cnt - 2 ? h : cnt - 2;
+    c.last = y >= n - out ? 1 : 0;
+    return c;
+}
+
+__device__ __forceinline__ int reflect101(int y, int n) {
+    y = y < 0 ? -y : y;
+    return y >= n ? 2 * (n - 1) - y : y;
+}
+
+// tiles [count][tile][tile][4] <- normalised mirrored windows of img [Cimg][H][W] (raw 0..255), tiles first .. first+count-1 in
+// row-major tile order.  pack_tiles_kernel's arithmetic, ((v - m) / s) / 255, channel 3 = 0; one channel is copied into three.
+template <bool U8>
+__global__ __launch_bounds__(256) void pack_tiles_reflect_kernel(const void* __restrict__ img_, int Cimg, int H, int W, int tile, int out,
+                                                                  int stride, int cols, int first, int count, float m0, float m1, float m2,
+                                                                  float s0, float s1, float s2, float* __restrict__ tiles) {
+    typedef typename std::conditional<U8, unsigned char, float>::type T;
+    const T* __restrict__ img = static_cast<const T*>(img_);
+    const int pad = (tile - out) / 2;
+    const long long total = (long long)count * tile * tile;
+    const size_t plane = (size_t)H * W;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c0 = (int)(i % tile);
+        const long long t = i / tile;
+        const int r = (int)(t % tile);
+        const int k = first + (int)(t / tile);
+        const int y = reflect101(overlap_origin(k / cols, H, out, stride) - pad + r, H);
+        const int x = reflect101(overlap_origin(k % cols, W, out, stride) - pad + c0, W);
+        const T* src = img + (size_t)y * W + x;
+        const float a = (float)src[0];
+        const float b = Cimg == 3 ? (float)src[plane] : a;
+        const float c = Cimg == 3 ? (float)src[2 * plane] : a;
+        ot_f32x4 v;
+        v.x = ((a - m0) / s0) / 255.f;
+        v.y = ((b - m1) / s1) / 255.f;
+        v.z = ((c - m2) / s2) / 255.f;
+        v.w = 0.f;
+        *reinterpret_cast<ot_f32x4*>(tiles + 4 * i) = v;
+    }
+}
+
+constexpr int kOtPx = 4;      // consecutive pixels per lane: the mask leaves as one dword per lane
+
+// logits [rows*cols][out][out][pitch] (NHWC tiles, row-major tile order) -> mask [H][W] (uint8), probs [C][H][W] (fp32, optional).
+// Lane q owns the linear pixels 4q .. 4q+3 (they may straddle a row or a tile edge: every pixel finds its own covering tiles); the
+// pixels are visited one after the other (a rolled loop: an unrolled one holding the four pixels' C means spills at C >= 9), the
+// mask bytes are collected and leave as one aligned dword.  probs, an optional extra output, is written per pixel.
+template <int C>
+__global__ __launch_bounds__(256) void stitch_overlap_kernel(const float* __restrict__ logits, OverlapGeom g, unsigned char* __restrict__ mask,
+                                                              float* __restrict__ probs) {
+    constexpr int NV = (C + 3) / 4;
+    const long long total = (long long)g.H * g.W;
+    const long long groups = cdiv<long long>(total, kOtPx);
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += (long long)gridDim.x * blockDim.x) {
+        const long long base = q * kOtPx;
+        const int np = total - base < kOtPx ? (int)(total - base) : kOtPx;
+        unsigned int packed = 0;
+#pragma unroll 1
+        for (int p = 0; p < np; ++p) {
+            const long long i = base + p;
+            const int y = (int)(i / g.W), x = (int)(i - (long long)y * g.W);
+            const Cover cy = overlap_cover(y, g.H, g.out, g.stride, g.rows);
+            const Cover cx = overlap_cover(x, g.W, g.out, g.stride, g.cols);
+            float acc[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = 0.f;
+            int n = 0;
+            for (int a = cy.lo; a <= cy.hi + cy.last; ++a) {
+                const int ti = a <= cy.hi ? a : g.rows - 1;
+                const int ly = y - overlap_origin(ti, g.H, g.out, g.stride);
+                for (int b = cx.lo; b <= cx.hi + cx.last; ++b) {
+                    const int tj = b <= cx.hi ? b : g.cols - 1;
+                    const int lx = x - overlap_origin(tj, g.W, g.out, g.stride);
+                    const ot_f32x4* src = reinterpret_cast<const ot_f32x4*>(
+                        logits + (((size_t)(ti * g.cols + tj) * g.out + ly) * g.out + lx) * g.pitch);
+                    float v[NV * 4];
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) {
+                        const ot_f32x4 t = src[k];
+                        v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w;
+                    }
+                    float m = v[0];
+#pragma unroll
+                    for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
+                    float s = 0.f;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) { v[c] = expf(v[c] - m); s += v[c]; }
+                    const float inv = 1.f / s;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) acc[c] += v[c] * inv;
+                    ++n;
+                }
+            }
+            const float fn = (float)n;
+            int best = 0;
+            float bv = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                acc[c] = acc[c] / fn;
+                if (c == 0 || acc[c] > bv) { bv = acc[c]; best = c; }     // first maximum (np.argmax)
+            }
+            packed |= (unsigned int)best << (8 * p);
+            if (probs != nullptr) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) probs[(size_t)c * total + i] = acc[c];
+            }
+        }
+        if (np == kOtPx) {
+            *reinterpret_cast<unsigned int*>(mask + base) = packed;     // base % 4 == 0: an aligned dword
+        } else {
+            for (int p = 0; p < np; ++p) mask[base + p] = (unsigned char)(packed >> (8 * p));
+        }
+    }
+}
+
+inline int ot_grid(long long n) {
+    const long long b = cdiv<long long>(n, 256);
+    return (int)(b < 8192 ? (b < 1 ? 1 : b) : 8192);
+}
+
+// the geometry both entry points accept (pylc_amd/inference.py:overlap_tile_grid raises on the same conditions)
+inline int overlap_check(const char* who, int H, int W, int out, int stride, int pad) {
+    PYLC_REQUIRE(out > 0 && pad >= 0, "%s: out=%d pad=%d", who, out, pad);
+    PYLC_REQUIRE(stride >= 1 && stride <= out, "%s: stride %d outside [1, out=%d]", who, stride, out);
+    PYLC_REQUIRE(H >= out && W >= out, "%s: image %dx%d smaller than the output tile %d", who, H, W, out);
+    PYLC_REQUIRE(pad < H && pad < W, "%s: pad %d must be below the image size %dx%d (one reflection)", who, pad, H, W);
+    return PYLC_OK;
+}
+
+}  // namespace
+}  // namespace pylc
+
+using namespace pylc;
+
+extern "C" int pylc_image_pack_tiles_reflect(const void* img, int is_u8, int Cimg, int H, int W, int tile, int out, int stride, int first_tile,
+                                             int n_tiles, const float* mean3, const float* std3, float* tiles, void* stream) {
+    PYLC_REQUIRE(img && tiles && mean3 && std3 && (Cimg == 1 || Cimg == 3) && tile > out && (tile - out) % 2 == 0,
+                 "image_pack_tiles_reflect: bad arguments");
+    if (int rc = overlap_check("image_pack_tiles_reflect", H, W, out, stride, (tile - out) / 2)) return rc;
+    const int rows = overlap_count(H, out, stride), cols = overlap_count(W, out, stride);
+    PYLC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (long long)first_tile + n_tiles <= (long long)rows * cols,
+                 "image_pack_tiles_reflect: tiles %d..%d outside the %dx%d grid", first_tile, first_tile + n_tiles - 1, rows, cols);
+    const long long total = (long long)n_tiles * tile * tile;
+    hipStream_t st = as_stream(stream);
+    if (is_u8)
+        hipLaunchKernelGGL(pack_tiles_reflect_kernel<true>, dim3(ot_grid(total)), dim3(256), 0, st, img, Cimg, H, W, tile, out, stride, cols,
+                           first_tile, n_tiles, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], tiles);
+    else
+        hipLaunchKernelGGL(pack_tiles_reflect_kernel<false>, dim3(ot_grid(total)), dim3(256), 0, st, img, Cimg, H, W, tile, out, stride, cols,
+                           first_tile, n_tiles, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], tiles);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_stitch_overlap_argmax(const float* logits, int pitch, int n_tiles, int H, int W, int out, int stride, int C,
+                                          unsigned char* mask, float* probs, void* stream) {
+    PYLC_REQUIRE(logits && mask && pitch >= C && pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0,
+                 "stitch_overlap_argmax: logits must be 16-B aligned NHWC tiles with a pitch >= C, multiple of 4");
+    if (int rc = overlap_check("stitch_overlap_argmax", H, W, out, stride, 0)) return rc;
+    const int rows = overlap_count(H, out, stride), cols = overlap_count(W, out, stride);
+    PYLC_REQUIRE((long long)rows * cols == n_tiles, "stitch_overlap_argmax: %d tiles given, the %dx%d grid needs %d", n_tiles, rows, cols,
+                 rows * cols);
+    const OverlapGeom g{H, W, out, stride, rows, cols, pitch};
+    const int blocks = ot_grid(cdiv<long long>((long long)H * W, kOtPx));
+    hipStream_t st = as_stream(stream);
+#define LAUNCH_OT(CC) hipLaunchKernelGGL((stitch_overlap_kernel<CC>), dim3(blocks), dim3(256), 0, st, logits, g, mask, probs)
+    switch (C) {
+        case 2: LAUNCH_OT(2); break; case 3: LAUNCH_OT(3); break; case 4: LAUNCH_OT(4); break; case 5: LAUNCH_OT(5); break;
+        case 6: LAUNCH_OT(6); break; case 7: LAUNCH_OT(7); break; case 8: LAUNCH_OT(8); break; case 9: LAUNCH_OT(9); break;
+        case 10: LAUNCH_OT(10); break; case 11: LAUNCH_OT(11); break; case 12: LAUNCH_OT(12); break; case 13: LAUNCH_OT(13); break;
+        case 14: LAUNCH_OT(14); break; case 15: LAUNCH_OT(15); break; case 16: LAUNCH_OT(16); break;
+        default: return fail(PYLC_ERR_ARG, "stitch_overlap_argmax: n_classes=%d unsupported (2..%d)", C, PYLC_MAX_CLASSES);
+    }
+#undef LAUNCH_OT
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}

@@ -7,7 +7,11 @@ here tiles are cut (and normalised) straight from the device image, logits stay 
 overlaps and takes the argmax, so only the uint8 class mask (1 byte per pixel) ever needs to leave the GPU.
 
 Out of scope here (host I/O in the reference): reading the image file and cv2-resizing it to a multiple of the tile
-size (utils/tools.py:77-206); callers pass the fitted image."""
+size (utils/tools.py:77-206); callers pass the fitted image.
+
+A U-Net of valid convolutions returns the centred (tile - 2*pad)^2 square of its window, which reconstruct() cannot stitch; its
+images take the overlap-tile path instead (predict_overlap_tile, csrc/overlap_tile.hip): mirror-padded windows around output tiles
+that cover the image exactly, at any image size, blended by the mean of the tiles' softmax probabilities."""
 import ctypes as C
 
 import torch
@@ -59,7 +63,11 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None):
     group=None (default): LOCAL -- this process runs every tile and returns the mask, also inside a data-parallel job (a rank-0-only
     validation preview must not hang in a collective).  With an explicit process group the call is a COLLECTIVE that every rank of the
     group must make: the tile batches are dealt round-robin over the ranks -- every rank holds the image and a replica of the model --
-    and the logit tiles are gathered to rank 0, which stitches; the other ranks return None."""
+    and the logit tiles are gathered to rank 0, which stitches; the other ranks return None.
+
+    A U-Net model (meta.arch == 'unet') takes predict_overlap_tile instead (any image size, stride default tile - 2*pad)."""
+    if model.meta.arch == 'unet':
+        return predict_overlap_tile(model, image, tile, stride, batch, group)
     L.init()
     stride = tile // 2 if stride is None else stride          # test.py:63
     dev = model.device
@@ -113,6 +121,112 @@ def stitch_logits(logits_tiles, rows, cols, tile, stride):
     mask = torch.empty((rows * stride + tile - stride, cols * stride + tile - stride), device=buf.device, dtype=torch.uint8)
     check(lib.pylc_stitch_argmax(ptr(buf), cp, rows, cols, tile, stride, c, ptr(mask), stream()))
     return mask
+
+
+# ---- overlap tiles for the valid-convolution U-Net (config.py:225-236: input_size 512, output_size 324, mirror padding) -------------
+def overlap_tile_grid(h, w, out, stride, pad=0):
+    """Output-tile origins (row_origins, col_origins) of an h x w image: o_i = min(i*stride, n - out) for i = 0 .. ceil((n - out) /
+    stride) along an axis of length n -- the last tile moved back to end at the image edge.  Tile (i, j) covers [o_i, o_i + out) x
+    [o_j, o_j + out) and reads the input window `pad` wider on every side, mirrored (reflect-101) beyond the image."""
+    if stride < 1:
+        raise ValueError('overlap tiles: stride %d < 1' % stride)
+    if stride > out:
+        raise ValueError('overlap tiles: stride %d > output tile %d would leave pixels uncovered (need stride <= out)' % (stride, out))
+    if h < out or w < out:
+        raise ValueError('overlap tiles: image %dx%d is smaller than the output tile %d (need H, W >= out)' % (h, w, out))
+    if pad >= h or pad >= w:
+        raise ValueError('overlap tiles: pad %d >= image side of %dx%d (need pad < H and pad < W: one mirror reflection)' % (pad, h, w))
+
+    def axis(n):
+        return [min(i * stride, n - out) for i in range(-(-(n - out) // stride) + 1)]
+    return axis(h), axis(w)
+
+
+def overlap_tile_out(net, tile, pad):
+    """Output tile side out = tile - 2*pad, checked against what the U-Net returns for a `tile` window (UNet.output_size): only
+    then does the output sit centred in its window, at offset pad (512 -> 324 and 256 -> 68 pass, 572 -> 388 and 252 -> 68 do not)."""
+    out = tile - 2 * pad
+    got = net.output_size(tile)
+    if got != out:
+        raise ValueError('overlap tiles: a %d px window gives a %d px U-Net output, not tile - 2*pad = %d (pad %d): the output would not be '
+                         'centred in its window' % (tile, got, out, pad))
+    return out
+
+
+def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=None, return_probs=False):
+    """Full-image U-Net inference by overlap tiles.  image: [C,H,W] raw 0..255, uint8 or float, host or device, any H, W >= out
+    (out = tile - 2*meta.pad_size; no fitting).  stride in [1, out], default out.  Returns the uint8 class mask [H,W] (device), or
+    (mask, probs) with probs the fp32 mean softmax probabilities [n_classes,H,W] when return_probs.
+
+    The mirrored windows are cut and normalised on the device (predict_image's statistics), run through model.net in eval mode in
+    batches of `batch`, and every logit tile stays in HBM until one kernel blends them: each pixel's class scores are the mean of the
+    softmax probabilities of the tiles covering it, its class their argmax.  `group`: predict_image's contract (batches dealt over the
+    ranks, logit tiles gathered to rank 0, which stitches and returns; the other ranks return None)."""
+    L.init()
+    if model.meta.arch != 'unet':
+        raise ValueError('predict_overlap_tile needs a U-Net (meta.arch == "unet"), got %r' % model.meta.arch)
+    pad = model.meta.pad_size
+    out = overlap_tile_out(model.net, tile, pad)
+    stride = out if stride is None else int(stride)
+    dev = model.device
+    u8 = image.dtype == torch.uint8            # a photograph: a quarter of the bytes to upload, normalised straight from them
+    img = image.to(dev, dtype=torch.uint8 if u8 else torch.float32).contiguous()
+    cimg, h, w = img.shape
+    if cimg != model.meta.ch:
+        raise ValueError('model expects %d-channel images' % model.meta.ch)
+    row_o, col_o = overlap_tile_grid(h, w, out, stride, pad)
+    n = len(row_o) * len(col_o)
+    mean, std, denom = model._stats(model.meta.normalize_default)
+    if denom != 255.0:                  # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
+        std = [v * denom / 255.0 for v in std]
+    world = dist.get_world_size(group) if group is not None else 1
+    rank = dist.get_rank(group) if group is not None else 0
+    mine = shard_batches(n, batch, rank, world)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    ncls = model.meta.n_classes
+    cp = (ncls + 3) & ~3
+    logits = torch.empty((sum(c for _, c in mine), out, out, cp), device=dev)
+    was_training = model.net.training
+    model.net.eval()
+    try:
+        model._refresh_for_inference()
+        with torch.no_grad():
+            pos = 0
+            for k, b in mine:
+                x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
+                check(lib.pylc_image_pack_tiles_reflect(ptr(img), int(u8), cimg, h, w, tile, out, stride, k, b, m, s, ptr(x4), stream()))
+                y = ops.as_nhwc(model.net(x4))                     # [b, ncls, out, out], NHWC memory
+                logits[pos:pos + b, :, :, :ncls].copy_(y.permute(0, 2, 3, 1))
+                pos += b
+    finally:
+        model.net.train(was_training)
+    if world > 1:
+        logits = gather_tiles(logits, n, batch, group)
+        if logits is None:
+            return None
+    return _stitch_overlap(logits, cp, n, h, w, out, stride, ncls, return_probs)
+
+
+def _stitch_overlap(buf, cp, n, h, w, out, stride, ncls, return_probs):
+    mask = torch.empty((h, w), device=buf.device, dtype=torch.uint8)
+    probs = torch.empty((ncls, h, w), device=buf.device) if return_probs else None
+    check(lib.pylc_stitch_overlap_argmax(ptr(buf), cp, n, h, w, out, stride, ncls, ptr(mask), ptr(probs), stream()))
+    return (mask, probs) if return_probs else mask
+
+
+def stitch_overlap_logits(logits_tiles, h, w, out, stride, return_probs=False):
+    """[n, C, out, out] logits of the overlap_tile_grid(h, w, out, stride) tiles in row-major order (any layout, device) -> uint8 class
+    mask [h, w] (and the mean probabilities [C, h, w] when return_probs): predict_overlap_tile's blend."""
+    L.init()
+    row_o, col_o = overlap_tile_grid(h, w, out, stride)
+    n, c = logits_tiles.shape[:2]
+    if n != len(row_o) * len(col_o) or tuple(logits_tiles.shape[2:]) != (out, out):
+        raise ValueError('stitch_overlap_logits: %s logits for a %dx%d grid of %d px tiles' % (tuple(logits_tiles.shape), len(row_o), len(col_o), out))
+    cp = (c + 3) & ~3
+    buf = torch.zeros((n, out, out, cp), device=logits_tiles.device)
+    buf[..., :c] = logits_tiles.permute(0, 2, 3, 1)
+    return _stitch_overlap(buf, cp, n, h, w, out, stride, c, return_probs)
 
 
 def colourize(mask, palette_rgb, out_h=None, out_w=None):

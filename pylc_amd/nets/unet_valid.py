@@ -98,6 +98,33 @@ class UNet(nn.Module):
             self.decoder.append(UNetUpBlock(prev, 2 ** (wf + i), padding, dropout, up_mode))
             prev = 2 ** (wf + i)
         self.last = Conv2d(prev, n_classes, 1, bias=True, init='torch')
+        self.padding = bool(padding)
+
+    def output_size(self, in_size):
+        """Side of the output for an in_size x in_size input, without running the network: per encoder block two 3x3 convs (-4 px each
+        block when valid), a floor 2x2 max-pool between blocks, then per decoder block a x2 up-sampling and two 3x3 convs
+        (512 -> 324, 256 -> 68).  Raises ValueError where a feature map would vanish or a skip tensor is smaller than the up-sampled
+        tensor its centre crop is concatenated with (unet.py:145-152)."""
+        shrink = 0 if self.padding else 4
+        s = int(in_size)
+        skips = []
+        for i in range(self.depth):
+            s -= shrink
+            if s < 1:
+                raise ValueError('U-Net input %d: the encoder block %d output vanishes' % (in_size, i))
+            if i < self.depth - 1:
+                skips.append(s)
+                s //= 2
+                if s < 1:
+                    raise ValueError('U-Net input %d: the max-pool after encoder block %d output vanishes' % (in_size, i))
+        for bridge in reversed(skips):
+            s *= 2
+            if bridge < s:
+                raise ValueError('U-Net input %d: skip tensor %d smaller than the up-sampled %d' % (in_size, bridge, s))
+            s -= shrink
+            if s < 1:
+                raise ValueError('U-Net input %d: a decoder block output vanishes' % in_size)
+        return s
 
     def forward(self, x):
         c = x.shape[1]
