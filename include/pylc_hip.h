@@ -35,7 +35,8 @@ extern "C" {
 #define PYLC_ERR_UNSUPPORTED 4   /* an optional run-time dependency is absent (pylc_comm_*: no loadable librccl) */
 
 const char* pylc_last_error(void);
-/* ABI version of this header (bumped on any signature change): 14 (pylc_image_pack_tiles_reflect, pylc_stitch_overlap_argmax). */
+/* ABI version of this header (bumped on any signature change): 15 (pylc_resize_area_u8, pylc_class_encode_resize,
+ * pylc_image_pack_tiles_ex). */
 int pylc_abi_version(void);
 /* 1 when the library was built with EXPERIMENTAL=1, i.e. the entry points inside #ifdef PYLC_EXPERIMENTAL below exist (pylc_amd/csrc/Makefile) */
 int pylc_experimental_build(void);
@@ -578,6 +579,29 @@ int pylc_image_pack_tiles_reflect(const void* img, int is_u8, int Cimg, int H, i
  * probs: NULL, or fp32 [C][H][W] receiving those means (the layout of the reference's mask_fullsized). C in 2..16. */
 int pylc_stitch_overlap_argmax(const float* logits, int pitch, int n_tiles, int H, int W, int out, int stride, int C,
                                unsigned char* mask, float* probs, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * Whole photographs (ABI 15, csrc/photo.hip): the reference's test path around the network (test.py:23-115).
+ * get_image's --scale resize (utils/tools.py:77-148) and adjust_to_tile's fit to the tile grid
+ * (utils/tools.py:151-206; Extractor.extract(fit=True, stride=tile//2), utils/extract.py:106-160) are
+ * cv2.resize(INTER_AREA); the ground truth is read with INTER_NEAREST and both masks are class-encoded through
+ * the schema palette (class_encode, utils/tools.py:412-449; Evaluator.load, utils/evaluate.py:64-118).
+ * ------------------------------------------------------------------------------------------- */
+/* OpenCV's general INTER_AREA downscale (resizeArea, computeResizeAreaTab) of a uint8 photograph: src is [H][W][Cimg]
+ * interleaved (src_planar = 0, a decoded image) or [Cimg][H][W] (src_planar = 1), Cimg 1 or 3; dst is planar uint8
+ * [Cimg][oh][ow], the layout the tile cutters read.  Per axis scale = 1 / (dst / src) in double; float weights, fp32
+ * accumulation in OpenCV's order (row sums over ascending columns, then acc += beta * rowsum over ascending rows), round to
+ * nearest even.  oh <= H and ow <= W (an error otherwise); equal sizes copy the bytes. */
+int pylc_resize_area_u8(const unsigned char* src, int src_planar, int Cimg, int H, int W, unsigned char* dst, int oh, int ow,
+                        void* stream);
+/* out[oy][ox] (uint8 class index) = class_encode of rgb[sy][sx][3], sy = min(floor(oy * (1 / (oh / H))), H - 1) in double
+ * (cv2.INTER_NEAREST; likewise sx): the LAST k with palette[k] == the colour, 1 when no entry matches (np.ones).
+ * palette_rgb: device uint8 [n_classes][3], n_classes <= PYLC_MAX_CLASSES.  oh == H, ow == W is plain encoding. */
+int pylc_class_encode_resize(const unsigned char* rgb, int H, int W, const unsigned char* palette_rgb, int n_classes,
+                             unsigned char* out, int oh, int ow, void* stream);
+/* pylc_image_pack_tiles on a float32 (is_u8 = 0) or uint8 (is_u8 = 1) image [Cimg][H][W]: same arguments and arithmetic,
+ * bit-identical tiles for equal pixel values (csrc/stitch.hip). */
+int pylc_image_pack_tiles_ex(const void* img, int is_u8, int Cimg, int H, int W, int tile, int stride, int first_tile,
+                             int n_tiles, const float* mean3, const float* std3, float* out, void* stream);
 
 /* Confusion matrix cm[t*C + p] += 1 over n pixels of class-index masks (uint8 or int64; *_bytes = 1 or 8); the scores of
  * utils/metrics.py:64-88 (weighted F1, weighted IoU = the "mIoU", MCC, normalised matrix) are functions of it.

@@ -8,7 +8,7 @@ int conv_init();
 
 extern "C" const char* pylc_last_error(void) { return pylc::g_err; }
 
-extern "C" int pylc_abi_version(void) { return 14; }      // r5: pylc_comm_*, PylcFwdEp, PylcConvDesc.w_planes_fmt, pylc_weight_prepare(interleave); 12: pylc_conv2d_wgrad_slabs, pylc_splitk_reduce_batch, PylcSlabSum; 13 (r6): pylc_comm_available; 14: pylc_image_pack_tiles_reflect, pylc_stitch_overlap_argmax
+extern "C" int pylc_abi_version(void) { return 15; }      // r5: pylc_comm_*, PylcFwdEp, PylcConvDesc.w_planes_fmt, pylc_weight_prepare(interleave); 12: pylc_conv2d_wgrad_slabs, pylc_splitk_reduce_batch, PylcSlabSum; 13 (r6): pylc_comm_available; 14: pylc_image_pack_tiles_reflect, pylc_stitch_overlap_argmax; 15: pylc_resize_area_u8, pylc_class_encode_resize, pylc_image_pack_tiles_ex
 
 // 1 when the library was built with EXPERIMENTAL=1 (include/pylc_hip.h: the #ifdef PYLC_EXPERIMENTAL entry points exist)
 extern "C" int pylc_experimental_build(void) {

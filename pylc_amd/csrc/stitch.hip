@@ -99,8 +99,9 @@ __global__ void colourize_resize_kernel(const unsigned char* __restrict__ mask, 
     }
 }
 
-// tiles [n][tile][tile][4] <- normalised window of img [Cimg][H][W] (raw 0..255); tile order row-major (extract.py:302-308)
-__global__ void pack_tiles_kernel(const float* __restrict__ img, int Cimg, int H, int W, int tile, int stride, int cols, int first, int count,
+// tiles [n][tile][tile][4] <- normalised window of img [Cimg][H][W] (raw 0..255, float or uint8); tile order row-major (extract.py:302-308)
+template <typename T>
+__global__ void pack_tiles_kernel(const T* __restrict__ img, int Cimg, int H, int W, int tile, int stride, int cols, int first, int count,
                                   float m0, float m1, float m2, float s0, float s1, float s2, float* __restrict__ out) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     const long long total = (long long)count * tile * tile;
@@ -111,10 +112,10 @@ __global__ void pack_tiles_kernel(const float* __restrict__ img, int Cimg, int H
         const int r = (int)(t % tile);
         const int k = first + (int)(t / tile);
         const int y = (k / cols) * stride + r, x = (k % cols) * stride + c0;
-        const float* src = img + (size_t)y * W + x;
-        const float a = src[0];
-        const float b = Cimg == 3 ? src[plane] : a;
-        const float c = Cimg == 3 ? src[2 * plane] : a;
+        const T* src = img + (size_t)y * W + x;
+        const float a = (float)src[0];
+        const float b = Cimg == 3 ? (float)src[plane] : a;
+        const float c = Cimg == 3 ? (float)src[2 * plane] : a;
         f32x4 v;
         v.x = ((a - m0) / s0) / 255.f;
         v.y = ((b - m1) / s1) / 255.f;
@@ -169,8 +170,24 @@ extern "C" int pylc_image_pack_tiles(const float* img, int Cimg, int H, int W, i
                  "image_pack_tiles: bad arguments");
     const int rows = (H - tile) / stride + 1, cols = (W - tile) / stride + 1;
     PYLC_REQUIRE(first_tile >= 0 && n_tiles > 0 && first_tile + n_tiles <= rows * cols, "image_pack_tiles: tile range outside the image");
-    hipLaunchKernelGGL(pack_tiles_kernel, dim3(grid_for((long long)n_tiles * tile * tile)), dim3(256), 0, as_stream(stream), img, Cimg, H, W, tile,
-                       stride, cols, first_tile, n_tiles, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], out);
+    hipLaunchKernelGGL(pack_tiles_kernel<float>, dim3(grid_for((long long)n_tiles * tile * tile)), dim3(256), 0, as_stream(stream), img, Cimg, H, W,
+                       tile, stride, cols, first_tile, n_tiles, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], out);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+// pylc_image_pack_tiles on a float (is_u8 = 0) or uint8 (is_u8 = 1) image: the same arguments, checks and arithmetic (a uint8 sample converts
+// to the float of the same value exactly), so equal pixel values give bit-identical tiles.  A photograph fitted on the device stays uint8.
+extern "C" int pylc_image_pack_tiles_ex(const void* img, int is_u8, int Cimg, int H, int W, int tile, int stride, int first_tile, int n_tiles,
+                                        const float* mean3, const float* std3, float* out, void* stream) {
+    if (!is_u8) return pylc_image_pack_tiles(static_cast<const float*>(img), Cimg, H, W, tile, stride, first_tile, n_tiles, mean3, std3, out, stream);
+    PYLC_REQUIRE(img && out && mean3 && std3 && (Cimg == 1 || Cimg == 3) && tile > 0 && stride > 0 && H >= tile && W >= tile,
+                 "image_pack_tiles_ex: bad arguments");
+    const int rows = (H - tile) / stride + 1, cols = (W - tile) / stride + 1;
+    PYLC_REQUIRE(first_tile >= 0 && n_tiles > 0 && first_tile + n_tiles <= rows * cols, "image_pack_tiles_ex: tile range outside the image");
+    hipLaunchKernelGGL(pack_tiles_kernel<unsigned char>, dim3(grid_for((long long)n_tiles * tile * tile)), dim3(256), 0, as_stream(stream),
+                       static_cast<const unsigned char*>(img), Cimg, H, W, tile, stride, cols, first_tile, n_tiles, mean3[0], mean3[1], mean3[2],
+                       std3[0], std3[1], std3[2], out);
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
 }

@@ -6,8 +6,8 @@ Counterpart of the reference's test path, test.py:50-110: Extractor(...).extract
 here tiles are cut (and normalised) straight from the device image, logits stay in HBM, and one kernel blends the
 overlaps and takes the argmax, so only the uint8 class mask (1 byte per pixel) ever needs to leave the GPU.
 
-Out of scope here (host I/O in the reference): reading the image file and cv2-resizing it to a multiple of the tile
-size (utils/tools.py:77-206); callers pass the fitted image.
+Reading the image file stays with the caller; resizing a photograph to a multiple of the tile size (utils/tools.py:77-206) and the
+steps after the stitch are pylc_amd.photo (segment_photo); the functions here take the fitted image.
 
 A U-Net of valid convolutions returns the centred (tile - 2*pad)^2 square of its window, which reconstruct() cannot stitch; its
 images take the overlap-tile path instead (predict_overlap_tile, csrc/overlap_tile.hip): mirror-padded windows around output tiles

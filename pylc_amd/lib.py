@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PYLC_LIB: load another build of the library (same-box A/B of two builds: tools/ab_builds.sh)
 LIB_PATH = os.environ.get('PYLC_LIB') or os.path.join(_HERE, 'libpylc_hip.so')
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class PylcError(RuntimeError):
@@ -182,6 +182,9 @@ SIGNATURES = {
     'pylc_colourize_resize': (_I, [_P, _I, _I, _P, _P, _I, _I, _P]),
     'pylc_image_pack_tiles_reflect': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     'pylc_stitch_overlap_argmax': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'pylc_resize_area_u8': (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    'pylc_class_encode_resize': (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P]),
+    'pylc_image_pack_tiles_ex': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     'pylc_image_pack_denom': (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _F, _P, _P]),
     'pylc_image_pack_u8': (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     'pylc_confusion_matrix': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P]),

@@ -1,0 +1,304 @@
+"""Whole photographs: the reference's test path (test.py:23-115) from a decoded image to the scaled-size class mask, its colour
+image and the reference's scores, with every pixel-sized step on the GPU.
+
+For each photograph the reference
+  1. reads it and, with --scale, resizes it by cv2.INTER_AREA (get_image, utils/tools.py:77-148);
+  2. fits it to the tile grid by a second INTER_AREA resize (adjust_to_tile, utils/tools.py:151-206, through
+     Extractor.extract(fit=True, stride=tile//2), utils/extract.py:106-160);
+  3. tiles, runs the network and stitches, colourises the mask and nearest-resizes it back to the scaled size
+     (utils/tools.py:209-319);
+  4. reads a ground-truth mask at the same scale by INTER_NEAREST, class-encodes both masks through the schema palette
+     (class_encode, utils/tools.py:412-449) and scores them per image or, with --aggregate_metrics, over all images
+     (utils/evaluate.py:64-176).
+
+Here steps 1-2 are pylc_resize_area_u8 (csrc/photo.hip: OpenCV's INTER_AREA weights and fp32 order), step 3 is predict_image's sliding
+window on the fitted uint8 image plus pylc_colourize_resize, and step 4 is pylc_class_encode_resize and pylc_confusion_matrix.  Decoding
+the image file is the caller's (PIL, imageio or cv2).
+
+A U-Net takes only the scale step and then predict_overlap_tile, which accepts any size: no fit and no resize back.  The reference has
+nothing to match there -- it cannot run a U-Net on a photograph at all (reconstruct() assumes same-size tiles)."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from . import metrics, ops, lib as L
+from .inference import gather_tiles, predict_overlap_tile, shard_batches, tile_grid
+from .lib import lib, check, ptr, stream
+
+MAX_CLASSES = 16            # PYLC_MAX_CLASSES (include/pylc_hip.h)
+
+
+# ---- geometry (host) ---------------------------------------------------------------------------------------------------------------
+def scaled_size(h, w, tile, scale=None):
+    """get_image's --scale arithmetic (utils/tools.py:125-134), literally: (int(scale * h), int(scale * w)), the scale first raised to
+    tile / min_dim when the short side is below the tile.  No scale (None or 0): the size itself."""
+    if not scale:
+        return h, w
+    min_dim = min(h, w)
+    if min_dim < tile:
+        scale = tile / min_dim
+    return int(scale * h), int(scale * w)
+
+
+def fit_geometry(h, w, tile, stride, scale=None):
+    """The reference's meta.extract sizes for an h x w photograph (utils/extract.py:160-170): w_full, h_full, w_scaled, h_scaled, w_fitted,
+    h_fitted, offset.  adjust_to_tile (utils/tools.py:182-204) restated in the same Python float arithmetic:
+    w_fitted = (w_scaled // tile) * tile, h_fitted = (ceil(w_fitted / aspect) // tile) * tile with aspect = w_scaled / h_scaled.
+
+    Raises ValueError when tile % stride != 0, when a resize would upscale (the scale step does exactly when the short side is below the
+    tile, or when scale > 1; the GPU resize downscales only), or when a fitted side would be 0."""
+    if stride <= 0 or stride > tile or tile % stride:
+        raise ValueError('tile %d is not a multiple of stride %d (adjust_to_tile, utils/tools.py:180)' % (tile, stride))
+    h_s, w_s = scaled_size(h, w, tile, scale)
+    if h_s > h or w_s > w:
+        raise ValueError('photograph %dx%d (HxW) at scale %s would be upscaled to %dx%d (short side below the tile %d?): INTER_AREA '
+                         'downscales only here' % (h, w, scale, h_s, w_s, tile))
+    if h_s == 0 or w_s == 0:
+        raise ValueError('photograph %dx%d (HxW) at scale %s has a side of 0' % (h, w, scale))
+    aspect = w_s / h_s
+    w_f = (w_s // tile) * tile
+    h_f = (math.ceil(w_f / aspect) // tile) * tile
+    if w_f == 0 or h_f == 0:
+        raise ValueError('photograph %dx%d (HxW, scaled %dx%d) fits to %dx%d tiles of %d: a side of 0' % (h, w, h_s, w_s, h_f, w_f, tile))
+    if h_f > h_s:
+        raise ValueError('fitting %dx%d to %dx%d would upscale' % (h_s, w_s, h_f, w_f))
+    # adjust_to_tile then crops h_resized - int(h_resized / tile) * tile rows off the top; h_f is already a multiple of the tile, so the
+    # crop -- the reference's `offset` -- is always 0
+    offset = h_f - int(h_f / tile) * tile
+    assert offset == 0
+    return {'w_full': w, 'h_full': h, 'w_scaled': w_s, 'h_scaled': h_s, 'w_fitted': w_f, 'h_fitted': h_f, 'offset': offset}
+
+
+# ---- device steps --------------------------------------------------------------------------------------------------------------
+def _upload_photo(image, device):
+    """[H,W,3] RGB or [H,W] / [H,W,1] grayscale uint8 (numpy or tensor) -> contiguous device uint8 [H,W,C] (one copy)."""
+    t = torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else torch.as_tensor(image)
+    if t.dtype != torch.uint8:
+        raise TypeError('a photograph must be uint8, got %s' % t.dtype)
+    if t.dim() == 2:
+        t = t.unsqueeze(-1)
+    if t.dim() != 3 or t.shape[2] not in (1, 3):
+        raise ValueError('a photograph must be [H,W,3] RGB or [H,W] / [H,W,1] grayscale, got %s' % (tuple(t.shape),))
+    return t.to(device).contiguous()
+
+
+def resize_area(img, oh, ow, planar=False):
+    """cv2.resize(INTER_AREA) of a device uint8 image, [H,W,C] interleaved (planar=False) or [C,H,W] (planar=True), to [C,oh,ow]."""
+    L.init()
+    if img.dtype != torch.uint8:
+        raise TypeError('resize_area needs uint8, got %s' % img.dtype)
+    img = img.contiguous()
+    c, h, w = img.shape if planar else (img.shape[2], img.shape[0], img.shape[1])
+    out = torch.empty((c, oh, ow), device=img.device, dtype=torch.uint8)
+    check(lib.pylc_resize_area_u8(ptr(img), int(planar), c, h, w, ptr(out), oh, ow, stream()))
+    return out
+
+
+def fit_image(image, tile, stride, scale=None, device='cuda'):
+    """Upload a photograph once and run the reference's two INTER_AREA resizes on the device: the --scale step when there is one, then the
+    fit to the tile grid.  Two launches, as two cv2.resize calls: the uint8 rounding between them is part of the reference's result.
+    Returns (device uint8 [C, h_fitted, w_fitted], fit_geometry dict)."""
+    L.init()
+    shape = tuple(image.shape)
+    geom = fit_geometry(shape[0], shape[1], tile, stride, scale)
+    img = _upload_photo(image, device)
+    h, w = geom['h_full'], geom['w_full']
+    h_s, w_s = geom['h_scaled'], geom['w_scaled']
+    if (h_s, w_s) != (h, w):
+        scaled = resize_area(img, h_s, w_s)
+        return resize_area(scaled, geom['h_fitted'], geom['w_fitted'], planar=True), geom
+    return resize_area(img, geom['h_fitted'], geom['w_fitted']), geom
+
+
+def _palette_tensor(palette, n_min, device):
+    pal = torch.as_tensor(np.asarray(palette, dtype=np.uint8)).reshape(-1, 3)
+    if pal.shape[0] < n_min or pal.shape[0] > MAX_CLASSES:
+        raise ValueError('palette needs %d..%d RGB entries, got %d' % (n_min, MAX_CLASSES, pal.shape[0]))
+    return pal.to(device).contiguous()
+
+
+def encode_mask(rgb, palette, out_hw=None, device=None):
+    """class_encode of an RGB mask [H,W,3] (uint8, numpy or tensor, host or device) through `palette` ([n][3]), nearest-resized to
+    out_hw = (oh, ow) first (cv2.INTER_NEAREST; default: its own size).  The last matching palette index wins, unmatched colours give 1
+    (utils/tools.py:412-449).  For a ground truth, out_hw is the photograph's (h_scaled, w_scaled).  Returns device uint8 [oh, ow]."""
+    L.init()
+    dev = device or (rgb.device if torch.is_tensor(rgb) and rgb.is_cuda else torch.device('cuda'))
+    t = _upload_photo(rgb, dev)
+    if t.shape[2] != 3:
+        raise ValueError('encode_mask needs an RGB mask [H,W,3], got %s' % (tuple(t.shape),))
+    h, w = t.shape[:2]
+    oh, ow = out_hw if out_hw is not None else (h, w)
+    pal = _palette_tensor(palette, 1, dev)
+    out = torch.empty((oh, ow), device=dev, dtype=torch.uint8)
+    check(lib.pylc_class_encode_resize(ptr(t), h, w, ptr(pal), pal.shape[0], ptr(out), oh, ow, stream()))
+    return out
+
+
+def _colourize(mask, pal, oh, ow):
+    out = torch.empty((oh, ow, 3), device=mask.device, dtype=torch.uint8)
+    check(lib.pylc_colourize_resize(ptr(mask), mask.shape[0], mask.shape[1], ptr(pal), ptr(out), oh, ow, stream()))
+    return out
+
+
+def _encode(rgb, pal):
+    out = torch.empty(rgb.shape[:2], device=rgb.device, dtype=torch.uint8)
+    check(lib.pylc_class_encode_resize(ptr(rgb), rgb.shape[0], rgb.shape[1], ptr(pal), pal.shape[0], ptr(out), rgb.shape[0], rgb.shape[1],
+                                       stream()))
+    return out
+
+
+# ---- the sliding window on a fitted uint8 image (predict_image's path, pylc_image_pack_tiles_ex) ------------------------------------
+def _predict_fitted(model, img, tile, stride, batch, group):
+    """predict_image (inference.py) on a device uint8 [C,H,W] fitted image: tiles cut by pylc_image_pack_tiles_ex, which gives the same
+    bytes as the float cutter, so the mask is bit-identical to predict_image on img.float()."""
+    dev = model.device
+    cimg, h, w = img.shape
+    rows, cols = tile_grid(h, w, tile, stride)
+    n = rows * cols
+    mean, std, denom = model._stats(model.meta.normalize_default)
+    if denom != 255.0:                  # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
+        std = [v * denom / 255.0 for v in std]
+    world = dist.get_world_size(group) if group is not None else 1
+    rank = dist.get_rank(group) if group is not None else 0
+    mine = shard_batches(n, batch, rank, world)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    ncls = model.meta.n_classes
+    cp = (ncls + 3) & ~3
+    logits = torch.empty((sum(c for _, c in mine), tile, tile, cp), device=dev)
+    with torch.no_grad():
+        pos = 0
+        for k, b in mine:
+            x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
+            check(lib.pylc_image_pack_tiles_ex(ptr(img), 1, cimg, h, w, tile, stride, k, b, m, s, ptr(x4), stream()))
+            y = model.net(x4)
+            if y.shape[2] != tile or y.shape[3] != tile:
+                raise ValueError('sliding-window stitching needs a same-size network (DeepLab); got %s' % (tuple(y.shape),))
+            p = ops.pitch_of(y)
+            logits[pos:pos + b].copy_(torch.as_strided(y, (b, tile, tile, cp), (tile * tile * p, tile * p, p, 1), y.storage_offset()))
+            pos += b
+    if world > 1:
+        logits = gather_tiles(logits, n, batch, group)
+        if logits is None:
+            return None
+    mask = torch.empty((h, w), device=dev, dtype=torch.uint8)
+    check(lib.pylc_stitch_argmax(ptr(logits), cp, rows, cols, tile, stride, ncls, ptr(mask), stream()))
+    return mask
+
+
+class PhotoResult:
+    """segment_photo's output.  mask: device uint8 [h_scaled, w_scaled] class indices; rgb: device uint8 [h_scaled, w_scaled, 3] when a
+    palette was given (else None); geometry: fit_geometry's dict; probs: the U-Net's mean softmax probabilities [n_classes, h_scaled,
+    w_scaled] when asked (else None).  tile and scale are what the ground truth's size is checked with (PhotoEvaluator.add)."""
+
+    def __init__(self, mask, rgb, geometry, probs, tile, scale):
+        self.mask, self.rgb, self.geometry, self.probs, self.tile, self.scale = mask, rgb, geometry, probs, tile, scale
+
+
+def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None, batch=8, group=None, return_probs=False):
+    """A decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1] grayscale uint8, numpy or tensor) -> PhotoResult at the scaled size.
+
+    DeepLab: fit (stride default tile // 2, test.py:63), predict_image's sliding window on the uint8 fitted image, pylc_colourize_resize
+    back to (h_scaled, w_scaled), then pylc_class_encode_resize of that colour image: the reference's round trip (colourize, resize,
+    class_encode), repeated palette colours included.  Without a palette the identity palette (k, k, k) gives the nearest-resized mask.
+
+    U-Net: the scale step only, then predict_overlap_tile at the scaled size (stride default its output tile); no fit, no resize back.
+
+    The model's channel count must match the image's; the network runs in eval mode and gets its mode back.  `group`: predict_image's
+    contract -- every rank fits its own copy and runs its share of the tile batches, rank 0 stitches, resizes and returns, the others
+    return None."""
+    L.init()
+    shape = tuple(image.shape)
+    ch = 1 if len(shape) == 2 else shape[2]
+    if ch != model.meta.ch:
+        raise ValueError('model expects %d-channel images, the photograph has %d' % (model.meta.ch, ch))
+    dev = model.device
+    unet = model.meta.arch == 'unet'
+    if return_probs and not unet:
+        raise ValueError('return_probs: only the U-Net blend has probabilities (the sliding-window stitch mixes logits and probabilities)')
+    pal = _palette_tensor(palette, model.meta.n_classes, dev) if palette is not None else None
+    was_training = model.net.training
+    model.net.eval()
+    try:
+        if unet:
+            h_s, w_s = scaled_size(shape[0], shape[1], tile, scale)
+            if h_s > shape[0] or w_s > shape[1] or h_s == 0 or w_s == 0:
+                raise ValueError('photograph %dx%d (HxW) at scale %s gives %dx%d: INTER_AREA downscales only here' % (shape[0], shape[1], scale,
+                                                                                                                       h_s, w_s))
+            geom = {'w_full': shape[1], 'h_full': shape[0], 'w_scaled': w_s, 'h_scaled': h_s, 'w_fitted': w_s, 'h_fitted': h_s,
+                    'offset': 0}                      # Extractor.extract(fit=False): (img, w_scaled, h_scaled, 0)
+            img = resize_area(_upload_photo(image, dev), h_s, w_s)      # at its own size: a relayout to [C,H,W]
+            got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs)
+            if got is None:
+                return None
+            mask, probs = got if return_probs else (got, None)
+            rgb = None
+            if pal is not None:
+                rgb = _colourize(mask, pal, h_s, w_s)
+                mask = _encode(rgb, pal)
+            return PhotoResult(mask, rgb, geom, probs, tile, scale)
+        stride = tile // 2 if stride is None else stride          # test.py:63
+        img, geom = fit_image(image, tile, stride, scale, dev)
+        fitted = _predict_fitted(model, img, tile, stride, batch, group)
+    finally:
+        model.net.train(was_training)
+    if fitted is None:
+        return None
+    h_s, w_s = geom['h_scaled'], geom['w_scaled']
+    enc = pal if pal is not None else torch.arange(model.meta.n_classes, device=dev, dtype=torch.uint8)[:, None].expand(-1, 3).contiguous()
+    rgb = _colourize(fitted, enc, h_s, w_s)
+    mask = _encode(rgb, enc)
+    return PhotoResult(mask, rgb if pal is not None else None, geom, None, tile, scale)
+
+
+# ---- scores ----------------------------------------------------------------------------------------------------------------------
+class PhotoEvaluator:
+    """The reference's Evaluator over segment_photo results, counts on the device (one int64 [C, C] matrix; nothing pixel-sized reaches the
+    host).  add() scores one image as Evaluator.evaluate() does (validate() overwrites the first C pixels: force_coverage);
+    aggregate() is the --aggregate_metrics result, where validate() overwrites the first C pixels of the CONCATENATION only
+    (utils/evaluate.py:150-176): the first image's counts with that coverage, every later image's without."""
+
+    def __init__(self, n_classes, palette):
+        self.n_classes = int(n_classes)
+        self.palette = np.asarray(palette, dtype=np.uint8).reshape(-1, 3)
+        if self.palette.shape[0] != self.n_classes:
+            raise ValueError('palette has %d entries for %d classes' % (self.palette.shape[0], self.n_classes))
+        self.cm = None
+        self.count = 0
+
+    def add(self, result, gt_rgb):
+        """Encode the ground-truth RGB mask ([H,W,3] uint8, full size) at the result's scaled size (get_image(scale, INTER_NEAREST)) and
+        score the result's mask against it.  A ground truth whose scaled size differs is an error (utils/evaluate.py:96-101).  Returns the
+        image's {'f1', 'iou', 'mcc', 'cmatrix'}."""
+        g = result.geometry
+        h_s, w_s = scaled_size(gt_rgb.shape[0], gt_rgb.shape[1], result.tile, result.scale)
+        if (h_s, w_s) != (g['h_scaled'], g['w_scaled']):
+            raise ValueError('ground truth mask dims (%dpx x %dpx) do not match predicted mask dims (%dpx x %dpx)' % (w_s, h_s, g['w_scaled'],
+                                                                                                                    g['h_scaled']))
+        y_true = encode_mask(gt_rgb, self.palette, (h_s, w_s), result.mask.device)
+        y_pred = result.mask
+        if y_pred.shape != y_true.shape:
+            raise ValueError('predicted mask %s vs ground truth %s' % (tuple(y_pred.shape), tuple(y_true.shape)))
+        cm = metrics.confusion_matrix(y_true, y_pred, self.n_classes, force_coverage=True)
+        plain = None if self.cm is None else metrics.confusion_matrix(y_true, y_pred, self.n_classes, force_coverage=False)
+        return self.add_counts(cm, plain)
+
+    def add_counts(self, cm_coverage, cm_plain=None):
+        """Accumulate one image given its count matrices with and without the coverage overwrite (device tensors, or host arrays for
+        counts made elsewhere); cm_plain is needed from the second image on.  Returns the image's scores (those of cm_coverage)."""
+        if self.cm is None:
+            self.cm = cm_coverage.clone() if torch.is_tensor(cm_coverage) else np.array(cm_coverage, dtype=np.int64)
+        else:
+            if cm_plain is None:
+                raise ValueError('add_counts: every image after the first needs its counts without coverage')
+            self.cm += cm_plain
+        self.count += 1
+        return metrics.scores(cm_coverage)
+
+    def aggregate(self):
+        if self.cm is None:
+            raise ValueError('aggregate evaluation: no images added')
+        return metrics.scores(self.cm)
