@@ -2,7 +2,9 @@
 pinned bit-exactly to the reference by make_golden.py) run with 1 and with 8 CPU threads -- two summation orders of one algorithm.  Per
 pinned gradient tensor the largest elementwise difference (relative to the tensor's largest entry) goes to tests/golden/truesize_conditioning.json;
 the GPU test uses it as the floor of its elementwise bound, exactly as test_nets_gpu.py uses the fixtures' `cond_maxdiff` (DESIGN.md section 3:
-a 101-layer train-mode network turns last-bit conv differences into per-cent gradient differences through ReLU flips).
+a 101-layer train-mode network turns last-bit conv differences into per-cent gradient differences through ReLU flips).  Every pinned tensor
+stays below 5 % of its largest entry (the largest: R101 layer4.2.conv2 4.8 %; Xception at bs 2: the ASPP's d = 12 filter 2.8 %, the image
+pool's conv 0.2 %), so an elementwise bound above this floor still says something for each of them.
 Run in the build container:  python tests/golden/make_truesize_conditioning.py      (needs no reference import: the oracle only)"""
 import json
 import os
@@ -21,8 +23,6 @@ def main():
     from tests.test_truesize_oracle_gpu import CASES, grad_keys
     out = {}
     for tag, (arch, backbone, n_cls, ch, b, hw, salt, seed) in CASES.items():
-        if arch == 'deeplab' and backbone == 'xception':
-            continue                                       # eval only
         cfg = ostep.StepConfig(arch, backbone, n_cls, ch, dropout=False)
         spec = oracle.state_spec(arch, backbone, n_cls, 3 if arch == 'deeplab' else ch)
         x = D.tiles(seed, b, ch, hw, hw)

@@ -79,6 +79,17 @@ CONV_FULL = [
     ('aspp 2048->256 3x3 d=6 @32^2 bs32 (aspp.py:18,61)', 2048, 256, 3, 1, 6, 6, 32, 32, 32, False),
     ('aspp 2048->256 3x3 d=18 @32^2 bs32 (aspp.py:18,67)', 2048, 256, 3, 1, 18, 18, 32, 32, 32, False),
     ('deeplab decoder 304->256 3x3 @128^2 bs32 (decoder.py:30)', 304, 256, 3, 1, 1, 1, 32, 128, 128, False),
+    # configs[4] (Aligned Xception, 1024^2 tiles, bs 8): every kind of 1x1 launch of the network -- thin K, ragged N (48 and 728 output
+    # channels), the wide exit flow, the strided skip projection -- and the two dense 3x3 convs of the stem, the first on the thin-input path
+    ('xception entry pointwise 64->128 1x1 @512^2 bs8 (xception.py:32,129)', 64, 128, 1, 1, 0, 1, 8, 512, 512, False),
+    ('deeplab decoder.conv1 128->48 1x1, ragged @256^2 bs8 (decoder.py:27)', 128, 48, 1, 1, 0, 1, 8, 256, 256, False),
+    ('xception block3 pointwise 256->728 1x1, ragged @128^2 bs8 (xception.py:32,132)', 256, 728, 1, 1, 0, 1, 8, 128, 128, False),
+    ('xception middle pointwise 728->728 1x1 @64^2 bs8 (xception.py:32,136)', 728, 728, 1, 1, 0, 1, 8, 64, 64, False),
+    ('xception block20 pointwise 728->1024 1x1 @64^2 bs8 (xception.py:32,170)', 728, 1024, 1, 1, 0, 1, 8, 64, 64, False),
+    ('xception exit pointwise 1536->2048 1x1 @64^2 bs8 (xception.py:32,179)', 1536, 2048, 1, 1, 0, 1, 8, 64, 64, False),
+    ('xception block3 skip 256->728 1x1 stride 2 128^2->64^2 bs8 (xception.py:48,132)', 256, 728, 1, 2, 0, 1, 8, 128, 128, False),
+    ('xception stem 3->32 3x3 stride 2 1024^2->512^2 bs8 (xception.py:122)', 3, 32, 3, 2, 1, 1, 8, 1024, 1024, False),
+    ('xception conv2 32->64 3x3 @512^2 bs8 (xception.py:126)', 32, 64, 3, 1, 1, 1, 8, 512, 512, False),
 ]
 
 
@@ -189,6 +200,8 @@ CONV_FULL_MODE3 = [
     ('deeplab decoder 256->256 3x3 @256^2 bs8 (decoder.py:30 at 1024^2 tiles)', 256, 256, 3, 1, 1, 1, 8, 256, 256, False),
     ('xception entry pointwise 128->128 1x1 @512^2 bs8 (xception.py:32,122)', 128, 128, 1, 1, 0, 1, 8, 512, 512, False),
     ('xception exit pointwise 1536->2048 1x1 @64^2 bs8 (xception.py:157)', 1536, 2048, 1, 1, 0, 1, 8, 64, 64, False),
+    ('xception block3 pointwise 256->728 1x1, ragged @128^2 bs8 (xception.py:32,132)', 256, 728, 1, 1, 0, 1, 8, 128, 128, False),
+    ('xception block20 pointwise 728->1024 1x1 @64^2 bs8 (xception.py:32,170)', 728, 1024, 1, 1, 0, 1, 8, 64, 64, False),
 ]
 
 
@@ -213,8 +226,10 @@ def test_conv_mode3_fwd_dgrad_wgrad_sampled_fp64(dev, mode3_full, case):
     _conv_case_sampled(dev, case, MODE3_TOL, MODE3_TOL, MODE3_TOL)
 
 
-@pytest.mark.parametrize('c,b,h,w,stride,dil', [(128, 8, 512, 512, 1, 1), (128, 8, 512, 512, 2, 1), (1536, 8, 64, 64, 1, 2), (728, 8, 64, 64, 1, 1)],
-                         ids=['entry 128 @512^2 stride 1', 'entry 128 @512^2 stride 2', 'exit 1536 @64^2 dilation 2', 'middle 728 @64^2'])
+@pytest.mark.parametrize('c,b,h,w,stride,dil', [(128, 8, 512, 512, 1, 1), (128, 8, 512, 512, 2, 1), (1536, 8, 64, 64, 1, 2), (728, 8, 64, 64, 1, 1),
+                                                (256, 8, 256, 256, 2, 1), (728, 8, 128, 128, 2, 1)],
+                         ids=['entry 128 @512^2 stride 1', 'entry 128 @512^2 stride 2', 'exit 1536 @64^2 dilation 2', 'middle 728 @64^2',
+                              'block2 256 @256^2 stride 2', 'block3 728 @128^2 stride 2'])
 def test_half_depthwise_tiled_kernels_fullsize(dev, c, b, h, w, stride, dil):
     """dw_tile_kernel / dw_tileg_kernel (one-plane fp16 tensors: stride 1, stride 2, dilation 2; xception.py:25-39 SeparableConv2d with
     fixed_padding) at the sizes of configs[4] (bs 8, 1024^2 tiles) -- the complete check of tests/test_round3_gpu.py (forward + statistics,
@@ -262,39 +277,85 @@ def test_dgrad_with_masked_residual_gradient_fullsize(dev, f16x3_full):
     del arena
 
 
-def test_depthwise_728_at_64sq_sampled_fp64(dev, f16x3_full):
-    """Xception middle flow at configs[4]'s size (728 channels, 64 x 64 map of a 1024^2 tile, bs 8; xception.py:34-39): depthwise 3x3 with
-    fixed_padding -- forward, input gradient and filter gradient of the product's default (fp32 tensor) path."""
+# every depthwise geometry of the Aligned Xception at configs[4]'s size (1024^2 tiles -> 512^2 maps after the stem, bs 8; output stride 16):
+# channels, map, stride, dilation (xception.py:25-39 with fixed_padding, Block :42-99, AlignedXception :122-179)
+DW_FULL = [(64, 512, 1, 1, 'block1.rep.0'), (128, 512, 1, 1, 'block1.rep.3'), (128, 512, 2, 1, 'block1.rep.6'),
+           (128, 256, 1, 1, 'block2.rep.0'), (256, 256, 1, 1, 'block2.rep.3'), (256, 256, 2, 1, 'block2.rep.6'),
+           (256, 128, 1, 1, 'block3.rep.1'), (728, 128, 1, 1, 'block3.rep.4'), (728, 128, 2, 1, 'block3.rep.7'),
+           (1024, 64, 1, 1, 'block20.rep.7'), (1024, 64, 1, 2, 'conv3'), (1536, 64, 1, 2, 'conv4, conv5')]
+
+
+def _depthwise_case_sampled(dev, C, H, stride, dil, name):
+    """Depthwise 3x3 with fixed_padding (a pad of `dil` on each side) at bs 8 through the product's default (fp32 tensor) path: forward,
+    input gradient, filter gradient and -- where the strip kernels emit them -- the statistics partials of the BatchNorm that follows,
+    against shifted-window float64 sums on the device:
+        y[b,c,p,q]  = sum_{r,s} x[b,c,p st - d + r d, q st - d + s d] w[c,r,s]
+        dx          = the same windows scattered back: dxp[b,c,p st + r d, q st + s d] += dy[b,c,p,q] w[c,r,s]   (dxp: x's padded frame)
+        dw[c,r,s]   = sum_{b,p,q} dy[b,c,p,q] x[b,c,p st - d + r d, q st - d + s d]"""
     from pylc_amd import ops
-    B, C, H, W = 8, 728, 64, 64
+    B, W = 8, H
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
     x = _nhwc(31, B, C, H, W, dev).requires_grad_(True)
     wt = (_rand(32, C, 1, 3, 3, dev=dev) * 0.3).requires_grad_(True)
-    y = ops.dwconv3x3(x, wt, 1, 1)
-    dy = _nhwc(33, B, C, H, W, dev)
+    y = ops.dwconv3x3(x, wt, stride, dil)
+    assert tuple(y.shape) == (B, C, OH, OW)
+    dy = _nhwc(33, B, C, OH, OW, dev)
     y.backward(dy)
     ops.sync_side_streams()
     torch.cuda.synchronize()
-    x64 = torch.nn.functional.pad(x.detach().double(), (1, 1, 1, 1))
+    d = dil
+    x64 = torch.nn.functional.pad(x.detach().double(), (d, d, d, d))
     w64 = wt.detach().double()
-    ref = torch.zeros(B, C, H, W, dtype=torch.float64, device=dev)
+    dy64 = dy.double()
+    ref = torch.zeros(B, C, OH, OW, dtype=torch.float64, device=dev)
     mag = torch.zeros_like(ref)
     refw = torch.zeros(C, 3, 3, dtype=torch.float64, device=dev)
-    dy64 = dy.double()
-    dyp = torch.nn.functional.pad(dy64, (1, 1, 1, 1))
-    refdx = torch.zeros_like(ref)
+    dxp = torch.zeros_like(x64)
     for r in range(3):
         for s in range(3):
-            win = x64[:, :, r:r + H, s:s + W]
-            ref += win * w64[:, 0, r, s][None, :, None, None]
-            mag += win.abs() * w64[:, 0, r, s].abs()[None, :, None, None]
+            rows, cols = slice(r * d, r * d + (OH - 1) * stride + 1, stride), slice(s * d, s * d + (OW - 1) * stride + 1, stride)
+            win = x64[:, :, rows, cols]
+            wrs = w64[:, 0, r, s][None, :, None, None]
+            ref += win * wrs
+            mag += win.abs() * wrs.abs()
             refw[:, r, s] = (dy64 * win).sum((0, 2, 3))
-            refdx += dyp[:, :, 2 - r:2 - r + H, 2 - s:2 - s + W] * w64[:, 0, r, s][None, :, None, None]
-    b, c, p, q = _samples(34, N_SAMPLES, dev, B, C, H, W)
+            dxp[:, :, rows, cols] += dy64 * wrs
+    refdx = dxp[:, :, d:d + H, d:d + W]
+    b, c, p, q = _samples(34, N_SAMPLES, dev, B, C, OH, OW)
     e_y = ((y.detach()[b, c, p, q].double() - ref[b, c, p, q]).abs() / (mag[b, c, p, q] + 1e-30)).max().item()
-    e_dx = ((x.grad[b, c, p, q].double() - refdx[b, c, p, q]).abs().max() / refdx.abs().max()).item()
+    b, c, h, wq = _samples(35, N_SAMPLES, dev, B, C, H, W)
+    e_dx = ((x.grad[b, c, h, wq].double() - refdx[b, c, h, wq]).abs().max() / refdx.abs().max()).item()
     e_dw = ((wt.grad[:, 0].double() - refw).abs().max() / refw.abs().max()).item()
-    print('depthwise 728 @64^2 bs8: y %.3g (of sum|ab|), dx %.3g, dw %.3g (of the largest entry)' % (e_y, e_dx, e_dw))
+    # the statistics partials (strip kernels: stride 1, dilation 1): same output bits, per-channel sums and sums of squares of the output
+    y2 = ops.dwconv3x3(x, wt, stride, dil, want_stats=True)
+    part = getattr(y2, '_pylc_sums', None)
+    assert (part is not None) == (stride == 1 and dil == 1)
+    e_st = float('nan')
+    if part is not None:
+        assert torch.equal(y2, y)
+        sums, yd = part.double().sum(0), y.detach().double()
+        s1, s2 = yd.sum((0, 2, 3)), (yd * yd).sum((0, 2, 3))
+        e_st = max(((sums[:C] - s1).abs().max() / s1.abs().max()).item(), ((sums[C:] - s2).abs().max() / s2.abs().max()).item())
+    del y2
+    print('depthwise %d @%d^2 stride %d dilation %d bs8 (%s): y %.3g (of sum|ab|), dx %.3g, dw %.3g (of the largest entry), statistics %.3g'
+          % (C, H, stride, dil, name, e_y, e_dx, e_dw, e_st))
     assert e_y < 1e-6 and e_dx < 2e-6 and e_dw < 5e-6          # tests/test_ops_gpu.py::test_dwconv's bounds
+    if part is not None:
+        assert e_st < 1e-5                                     # (test_dwconv's bound on the partials)
+
+
+def test_depthwise_728_at_64sq_sampled_fp64(dev, f16x3_full):
+    """Xception middle flow at configs[4]'s size (728 channels, 64 x 64 map of a 1024^2 tile, bs 8; xception.py:34-39): depthwise 3x3 with
+    fixed_padding -- forward, input gradient and filter gradient of the product's default (fp32 tensor) path."""
+    _depthwise_case_sampled(dev, 728, 64, 1, 1, 'middle flow, block20.rep.1 / rep.4')
+
+
+@pytest.mark.parametrize('C,H,stride,dil,name', DW_FULL, ids=['%d @%d^2 stride %d dil %d' % g[:4] for g in DW_FULL])
+def test_depthwise_xception_geometries_sampled_fp64(dev, f16x3_full, C, H, stride, dil, name):
+    """The other depthwise geometries of configs[4] (DW_FULL) at bs 8, checked as test_depthwise_728_at_64sq_sampled_fp64: strided and
+    dilated windows, maps from 64^2 to 512^2, the filter-gradient reduction over up to 2 M rows."""
+    _depthwise_case_sampled(dev, C, H, stride, dil, name)
+    torch.cuda.empty_cache()
 
 
 def test_batchnorm_524288x256_against_fp64(dev, f16x3_full):
