@@ -603,6 +603,28 @@ int pylc_class_encode_resize(const unsigned char* rgb, int H, int W, const unsig
 int pylc_image_pack_tiles_ex(const void* img, int is_u8, int Cimg, int H, int W, int tile, int stride, int first_tile,
                              int n_tiles, const float* mean3, const float* std3, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training tile sets (csrc/dataset.hip): the reference's `pylc.py extract` (Extractor.extract -> __split,
+ * utils/extract.py:106-231, 279-310) and the sums its dataset profile is made of (utils/profile.py:92-150).
+ * Integer arithmetic only: the results are exact and independent of band_rows and of first_tile chunking.
+ * ------------------------------------------------------------------------------------------- */
+/* img: device uint8 [Cimg][H][W] (Cimg 1 or 3, as pylc_resize_area_u8 writes it); mask: NULL or device uint8 class indices
+ * [H][W].  Writes tiles first_tile .. first_tile+n_tiles-1 of the grid rows = (H - tile) / stride + 1, cols = (W - tile) /
+ * stride + 1 (row-major; the remainder right and below is dropped: torch.unfold(0, tile, stride).unfold(1, tile, stride), the
+ * grid of pylc_image_pack_tiles_ex) as img_tiles [n][Cimg][tile][tile] and, with a mask, mask_tiles [n][tile][tile].  In
+ * the same pass it ADDS into sums [n][2][Cimg] the tile's sum of x (index 0) and of x^2 (index 1) per channel and, with a
+ * mask, into hist [n][n_classes + 1] the tile's class counts, every mask value >= n_classes in the last bin
+ * (1 <= n_classes <= PYLC_MAX_CLASSES).  sums and hist are indexed from first_tile and must be zeroed by the caller.
+ * band_rows: tile rows per block (a tile is cut by ceil(tile / band_rows) blocks), 0 for the default; band_rows * tile <=
+ * 65536.  tile > H or W, stride <= 0, n_classes out of range or a tile range beyond the grid: PYLC_ERR_ARG. */
+int pylc_extract_tiles(const unsigned char* img, int Cimg, int H, int W, const unsigned char* mask, int n_classes, int tile,
+                       int stride, int first_tile, int n_tiles, int band_rows, unsigned char* img_tiles,
+                       unsigned char* mask_tiles, unsigned long long* sums, unsigned long long* hist, void* stream);
+/* The same sums and histograms for tiles that already exist on the device: img_tiles [n][Cimg][tile][tile], mask_tiles NULL
+ * or [n][tile][tile]; sums [n][2][Cimg], hist [n][n_classes + 1], zeroed by the caller. */
+int pylc_tile_stats(const unsigned char* img_tiles, long long n_tiles, int Cimg, int tile, const unsigned char* mask_tiles,
+                    int n_classes, int band_rows, unsigned long long* sums, unsigned long long* hist, void* stream);
+
 /* Confusion matrix cm[t*C + p] += 1 over n pixels of class-index masks (uint8 or int64; *_bytes = 1 or 8); the scores of
  * utils/metrics.py:64-88 (weighted F1, weighted IoU = the "mIoU", MCC, normalised matrix) are functions of it.
  * force_coverage applies Evaluator.validate()'s overwrite of the first C pixels (utils/evaluate.py:171-174). cm must be

@@ -1,0 +1,468 @@
+"""Training tile sets from photographs: the reference's `pylc.py extract` (Extractor.extract -> __split -> class_encode -> coshuffle ->
+profile, utils/extract.py:106-231, 279-310; utils/profile.py:21-150; utils/metrics.py:90-132) and the oversampling-rate search of
+`pylc.py augment` (Augmentor.optimize, utils/augment.py:92-182), with every pixel-sized step on the GPU.
+
+For each image / mask pair the reference
+  1. reads the image and, with --scale, resizes it by cv2.INTER_AREA (get_image), optionally fits it to the tile grid (adjust_to_tile);
+  2. reads the mask at the same scale by cv2.INTER_NEAREST;
+  3. unfolds both into tile x tile tiles at `stride` (the remainder right and below is dropped) and class-encodes the mask tiles;
+  4. later walks over all tiles once more for the profile: per-tile channel mean and std, per-tile class histogram, and from the
+     histograms the class probabilities, the class weights of the weighted loss, M2 and the JSD against the uniform distribution.
+
+Here steps 1-2 are photo.resize_area / photo.fit_image / photo.encode_mask (nearest-resize then encode: the same pixels as encode after
+resize, since a nearest resize only selects pixels), step 3 is pylc_extract_tiles, which in the same pass leaves per tile the integer sums
+the profile is made of (sum x, sum x^2 per channel, the class histogram); step 4 is double arithmetic on those exact integers on the host.
+A TileSet keeps the tiles on the device (or in pinned host memory) and hands Model.train its batches.
+
+Out of scope: the augmentation transform itself (perspective_shift, utils/tools.py:557-594), HDF5 files, file collation, print_meta."""
+import math
+
+import numpy as np
+import torch
+
+from . import lib as L
+from . import photo
+from .lib import lib, check, ptr, stream
+
+MAX_CLASSES = photo.MAX_CLASSES
+
+
+# ---- geometry (host) ---------------------------------------------------------------------------------------------------------------
+def tile_grid_counts(h, w, tile, stride):
+    """(rows, cols) of torch.unfold(0, tile, stride).unfold(1, tile, stride) on an h x w image: (h - tile) // stride + 1 and likewise;
+    the remainder right and below is dropped.  ValueError when a side is below the tile."""
+    if tile <= 0 or stride <= 0:
+        raise ValueError('tile %d and stride %d must be positive' % (tile, stride))
+    if h < tile or w < tile:
+        raise ValueError('image %dx%d (HxW) is smaller than the tile %d' % (h, w, tile))
+    return (h - tile) // stride + 1, (w - tile) // stride + 1
+
+
+def _check_n_classes(n_classes):
+    if not 1 <= int(n_classes) <= MAX_CLASSES:
+        raise ValueError('n_classes=%s outside 1..%d' % (n_classes, MAX_CLASSES))
+    return int(n_classes)
+
+
+# ---- device steps --------------------------------------------------------------------------------------------------------------
+def _u8(t, what):
+    if t.dtype != torch.uint8:
+        raise TypeError('%s must be uint8, got %s' % (what, t.dtype))
+    return t.contiguous()
+
+
+def cut_tiles(img, mask=None, tile=512, stride=None, n_classes=None, first_tile=0, n_tiles=None, band_rows=0):
+    """pylc_extract_tiles on a device uint8 image [C,H,W] and, optionally, its class-index mask [H,W]: tiles first_tile ..
+    first_tile + n_tiles - 1 of the grid (default: all).  Returns (img_tiles [n,C,t,t] uint8, mask_tiles [n,t,t] uint8 or None,
+    sums int64 [n,2,C] -- sum x and sum x^2 per channel --, hist int64 [n, n_classes + 1] or None; the last bin counts every mask value
+    >= n_classes).  band_rows (tile rows per block, 0: the default) changes the launch only, never the result."""
+    L.init()
+    img = _u8(img, 'the image')
+    c, h, w = img.shape
+    stride = tile if stride is None else stride
+    n_all = 0
+    if 0 < tile <= min(h, w) and stride > 0:
+        rows, cols = tile_grid_counts(h, w, tile, stride)
+        n_all = rows * cols
+    n = max(n_all - first_tile, 0) if n_tiles is None else n_tiles
+    dev = img.device
+    out = torch.empty((max(n, 0), c, tile, tile), device=dev, dtype=torch.uint8)
+    sums = torch.zeros((max(n, 0), 2, c), device=dev, dtype=torch.int64)
+    mout = hist = None
+    if mask is not None:
+        mask = _u8(mask, 'the mask')
+        if tuple(mask.shape) != (h, w):
+            raise ValueError('mask %s does not match the image %dx%d' % (tuple(mask.shape), h, w))
+        mout = torch.empty((max(n, 0), tile, tile), device=dev, dtype=torch.uint8)
+        hist = torch.zeros((max(n, 0), (n_classes or 0) + 1), device=dev, dtype=torch.int64)
+    check(lib.pylc_extract_tiles(ptr(img), c, h, w, ptr(mask), n_classes or 0, tile, stride, first_tile, n, band_rows, ptr(out), ptr(mout),
+                                 ptr(sums), ptr(hist), stream()))
+    return out, mout, sums, hist
+
+
+def tile_stats(img, mask=None, n_classes=None, band_rows=0):
+    """pylc_tile_stats: cut_tiles' sums and histograms for device tiles that already exist ([n,C,t,t] uint8, masks [n,t,t] uint8)."""
+    L.init()
+    img = _u8(img, 'tiles')
+    if img.dim() != 4 or img.shape[2] != img.shape[3]:
+        raise ValueError('tiles must be [n,C,t,t], got %s' % (tuple(img.shape),))
+    n, c, t = img.shape[0], img.shape[1], img.shape[2]
+    sums = torch.zeros((n, 2, c), device=img.device, dtype=torch.int64)
+    hist = None
+    if mask is not None:
+        mask = _u8(mask, 'mask tiles')
+        if tuple(mask.shape) != (n, t, t):
+            raise ValueError('mask tiles %s do not match the tiles %s' % (tuple(mask.shape), tuple(img.shape)))
+        hist = torch.zeros((n, (n_classes or 0) + 1), device=img.device, dtype=torch.int64)
+    check(lib.pylc_tile_stats(ptr(img), n, c, t, ptr(mask), n_classes or 0, band_rows, ptr(sums), ptr(hist), stream()))
+    return sums, hist
+
+
+class Extracted:
+    """extract_photo's output.  img: device uint8 [n,C,t,t]; mask: device uint8 [n,t,t] class indices or None; sums: device int64
+    [n,2,C] (per tile and channel, sum x and sum x^2); hist: device int64 [n, n_classes + 1] or None (the last bin, values >= n_classes,
+    is all zero: extract_photo raises otherwise); geometry: the reference's meta.extract fields (photo.fit_geometry's, plus n)."""
+
+    def __init__(self, img, mask, sums, hist, geometry, tile, stride, n_classes):
+        self.img, self.mask, self.sums, self.hist, self.geometry = img, mask, sums, hist, geometry
+        self.tile, self.stride, self.n_classes = tile, stride, n_classes
+
+
+def _check_bad_classes(hist, n_classes):
+    bad = int(hist[:, -1].sum())
+    if bad:
+        raise ValueError('%d mask pixels hold a class index >= n_classes=%d (one_hot in utils/profile.py:109 would raise)' % (bad, n_classes))
+
+
+def extract_photo(image, mask_rgb=None, palette=None, tile=512, stride=None, scale=None, fit=False, n_classes=None, device='cuda'):
+    """One image / mask pair through Extractor.extract (utils/extract.py:133-215): a decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1]
+    grayscale uint8) and, optionally, its RGB mask [H,W,3] with the schema palette -> Extracted.
+
+    The image is uploaded once, scaled by get_image's arithmetic (photo.scaled_size, INTER_AREA) when `scale` is given, and cut by one
+    launch of pylc_extract_tiles.  The mask is nearest-resized to the same scaled size and class-encoded (photo.encode_mask).  stride
+    defaults to the tile (config.py:137); n_classes to the palette's length.
+
+    fit=True applies adjust_to_tile's second resize (photo.fit_image) and is allowed WITHOUT a mask only: the reference fits the image
+    but not the mask (extract.py:154-156 against :188-195), so its own image and mask tile counts diverge there.
+
+    ValueError: fit with a mask; a mask without a palette; n_classes outside 1..16; a resize that would upscale; image and mask scaled sizes
+    that differ (the assertion at extract.py:191); a scaled side below the tile; a mask pixel whose class index is >= n_classes."""
+    stride = tile if stride is None else stride
+    if fit and mask_rgb is not None:
+        raise ValueError('fit=True with a mask: the reference fits the image but not the mask (utils/extract.py:154-156, 188-195), so '
+                         'their tiles would not correspond')
+    if mask_rgb is not None and palette is None:
+        raise ValueError('a mask needs the schema palette')
+    if n_classes is None and palette is not None:
+        n_classes = len(palette)
+    if n_classes is not None:
+        n_classes = _check_n_classes(n_classes)
+    shape = tuple(image.shape)
+    h, w = shape[0], shape[1]
+    if fit:
+        geom = photo.fit_geometry(h, w, tile, stride, scale)
+        h_c, w_c = geom['h_fitted'], geom['w_fitted']
+    else:
+        h_s, w_s = photo.scaled_size(h, w, tile, scale)
+        if h_s > h or w_s > w:
+            raise ValueError('photograph %dx%d (HxW) at scale %s would be upscaled to %dx%d (short side below the tile %d?): INTER_AREA '
+                             'downscales only here' % (h, w, scale, h_s, w_s, tile))
+        if h_s == 0 or w_s == 0:
+            raise ValueError('photograph %dx%d (HxW) at scale %s has a side of 0' % (h, w, scale))
+        geom = {'w_full': w, 'h_full': h, 'w_scaled': w_s, 'h_scaled': h_s, 'w_fitted': w_s, 'h_fitted': h_s, 'offset': 0}
+        h_c, w_c = h_s, w_s
+    rows, cols = tile_grid_counts(h_c, w_c, tile, stride)
+    if mask_rgb is not None:
+        mh_s, mw_s = photo.scaled_size(mask_rgb.shape[0], mask_rgb.shape[1], tile, scale)
+        if (mh_s, mw_s) != (geom['h_scaled'], geom['w_scaled']):
+            raise ValueError('mask dims (%dpx x %dpx) do not match image dims (%dpx x %dpx) at scale %s' % (mw_s, mh_s, geom['w_scaled'],
+                                                                                                             geom['h_scaled'], scale))
+    L.init()
+    if fit:
+        img, _ = photo.fit_image(image, tile, stride, scale, device)
+    else:
+        img = photo.resize_area(photo._upload_photo(image, device), h_c, w_c)       # at its own size: a relayout to [C,H,W]
+    mask = None
+    if mask_rgb is not None:
+        mask = photo.encode_mask(mask_rgb, palette, (h_c, w_c), img.device)
+    tiles, mtiles, sums, hist = cut_tiles(img, mask, tile, stride, n_classes if mask is not None else None)
+    if hist is not None:
+        _check_bad_classes(hist, n_classes)
+    geom = dict(geom, n=rows * cols)
+    return Extracted(tiles, mtiles, sums, hist, geom, tile, stride, n_classes)
+
+
+# ---- the profile (host, double arithmetic on exact integers) ---------------------------------------------------------------------
+def jsd(p, q):
+    """utils/metrics.py:90-111, eps in the same places"""
+    eps = 1e-8
+    m = 0.5 * (p + q + eps)
+    return 0.5 * np.sum(np.multiply(p, np.log(p / m + eps))) + 0.5 * np.sum(np.multiply(q, np.log(q / m + eps)))
+
+
+def m2(p, n_classes):
+    """utils/metrics.py:114-132"""
+    if n_classes <= 1:
+        raise ValueError('M2 variance needs more than one class')
+    return (n_classes / (n_classes - 1)) * (1 - np.sum(p ** 2))
+
+
+def profile_from_sums(sums, hist, tile, n_classes):
+    """get_profile (utils/profile.py:92-148) from per-tile integer sums: sums int [n,2,C] (sum x, sum x^2), hist int [n, n_classes].
+
+    Per tile and channel, with N = tile^2: mean = S / N and the unbiased std = sqrt((N * SS - S^2) / (N * (N - 1))) -- torch.mean /
+    torch.std over (0, 2, 3) of a [1,C,t,t] batch; for one channel the reference pools over the whole tile, which is the same thing.
+    px_mean and px_std are the MEANS OVER TILES of these per-tile values: that is the reference's definition, which its networks were
+    trained with; px_std is therefore NOT the standard deviation of the dataset's pixels (it leaves out the spread between tiles).
+
+    Returns a dict under the reference's meta names: n_samples, tile_px_count, px_mean, px_std, px_dist [n][n_classes], dset_px_dist,
+    dset_px_count, probs, weights (1 / ln(1.02 + probs), normalised by its maximum), m2, jsd (against the uniform distribution)."""
+    sums = np.asarray(sums)
+    hist = np.asarray(hist, dtype=np.int64)
+    n, _, c = sums.shape
+    if n == 0:
+        raise ValueError('profile of an empty tile set')
+    N = int(tile) * int(tile)
+    mean = np.empty((n, c))
+    std = np.empty((n, c))
+    for i in range(n):                                   # python integers: N * SS and S^2 pass 2^63 from tiles of 8192^2 on
+        for k in range(c):
+            s, ss = int(sums[i, 0, k]), int(sums[i, 1, k])
+            mean[i, k] = s / N
+            std[i, k] = math.sqrt((N * ss - s * s) / (N * (N - 1)))
+    px_dist = hist[:, :n_classes]
+    dset_px_dist = np.sum(px_dist, axis=0)
+    dset_px_count = np.sum(dset_px_dist)
+    if int(dset_px_count) != n * N:
+        raise ValueError('pixel distribution (%d) does not match the tile count (%d x %d)' % (int(dset_px_count), n, N))
+    probs = dset_px_dist / dset_px_count
+    weights = 1 / (np.log(1.02 + probs))
+    weights = weights / np.max(weights)
+    balanced = np.empty(n_classes)
+    balanced.fill(1 / n_classes)
+    return {'n_samples': n, 'tile_size': int(tile), 'tile_px_count': N, 'ch': c, 'n_classes': int(n_classes),
+            'px_mean': (mean.sum(0) / n).tolist(), 'px_std': (std.sum(0) / n).tolist(),
+            'px_dist': px_dist.tolist(), 'dset_px_dist': dset_px_dist.tolist(), 'dset_px_count': int(dset_px_count),
+            'probs': probs.tolist(), 'weights': weights.tolist(), 'm2': float(m2(probs, n_classes)), 'jsd': float(jsd(probs, balanced))}
+
+
+def oversample_rates(profile, rate_coef_range=(1, 21), threshold_range=(0, 3.), rate_range=(0, 4), n_samples_ratio=0.36):
+    """Augmentor.optimize (utils/augment.py:100-180) on a profile dict, in the same numpy dtypes and operation order: per-tile scores from
+    the class histograms, a grid over rate coefficients (step 1) and thresholds (step 0.05), rates = int(coef * score) where the score
+    passes the threshold, clipped to rate_range; of the candidates that add fewer than int(n_samples_ratio * n) tiles, the first one of
+    least JSD against the uniform distribution.  Returns {'rates' (int array [n]: copies to add per tile), 'threshold', 'rate_coef',
+    'probs', 'n_samples', 'aug_n_samples', 'jsd', 'm2'}.  ValueError where the reference asserts 'No augmentation optimization found'."""
+    eps = 1e-8
+    px_dist = np.array(profile['px_dist'], dtype='long')
+    px_count = profile['tile_px_count']
+    n_classes = px_dist.shape[1]
+    input_size = px_dist.shape[0]
+    dset_probs = np.array(profile['probs'], dtype='float32') + eps
+    oversample_filter = np.clip(1 / n_classes - dset_probs, a_min=0, a_max=1.)
+    probs = px_dist / px_count
+    probs_weighted = np.multiply(np.multiply(probs, 1 / dset_probs), oversample_filter)
+    scores = np.sqrt(np.sum(probs_weighted, axis=1))
+    rate_coefs = np.arange(min(rate_coef_range), max(rate_coef_range), 1.)
+    thresholds = np.arange(min(threshold_range), max(threshold_range), 0.05)
+    balanced = np.empty(n_classes)
+    balanced.fill(1 / n_classes)
+    jsds, found = [], []
+    for rate_coef in rate_coefs:
+        for threshold in thresholds:
+            over_sample = scores > threshold
+            rates = np.multiply(over_sample, rate_coef * scores).astype(int)
+            rates = np.clip(rates, rate_range[0], rate_range[1])
+            if np.sum(rates) < int(n_samples_ratio * input_size):
+                aug_px_dist = np.multiply(np.expand_dims(rates, axis=1), px_dist)
+                full_px_dist = px_dist + aug_px_dist
+                full_px_probs = np.sum(full_px_dist, axis=0) / np.sum(full_px_dist)
+                m2_sample = m2(full_px_probs, n_classes)
+                jsd_sample = jsd(full_px_probs, balanced)
+                jsds.append(jsd_sample)
+                found.append({'probs': full_px_probs, 'threshold': float(threshold), 'rate_coef': float(rate_coef), 'rates': rates,
+                              'n_samples': int(np.sum(full_px_dist) / px_count), 'aug_n_samples': int(np.sum(rates)),
+                              'jsd': float(jsd_sample), 'm2': float(m2_sample)})
+    if not jsds:
+        raise ValueError('No augmentation optimization found.')
+    return found[int(np.argmin(np.asarray(jsds)))]
+
+
+# ---- the container -------------------------------------------------------------------------------------------------------------
+def _pinned(shape):
+    t = torch.empty(shape, dtype=torch.uint8)
+    return t.pin_memory() if torch.cuda.is_available() else t
+
+
+class _Batches:
+    """re-iterable over a TileSet's (img uint8 [B,C,t,t], mask uint8 [B,t,t]) batches"""
+
+    def __init__(self, tiles, batch_size, drop_last):
+        self.tiles, self.batch_size, self.drop_last = tiles, int(batch_size), drop_last
+        if self.batch_size <= 0:
+            raise ValueError('batch_size=%s' % batch_size)
+
+    def __len__(self):
+        n = len(self.tiles)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def __iter__(self):
+        ts = self.tiles
+        img, mask = ts._storage()
+        for k in range(len(self)):
+            lo = ts.start + k * self.batch_size
+            hi = min(lo + self.batch_size, ts.end)
+            if ts.keep == 'device':
+                idx = torch.arange(lo, hi, device=img.device)
+                yield img.index_select(0, idx), (mask.index_select(0, idx) if mask is not None else None)
+            else:
+                yield img[lo:hi].numpy(), (mask[lo:hi].numpy() if mask is not None else None)
+
+
+class TileSet:
+    """Tiles of one size with their integer statistics, resident on the device (keep='device') or in pinned host memory (keep='host');
+    the statistics always end on the host (numpy int64).  add() appends extract_photo's output, from_arrays() takes tiles cut elsewhere
+    (their statistics come from pylc_tile_stats), coshuffle() permutes everything alike, partition() is a view, batches() feeds
+    Model.train and profile() is the reference's dataset profile."""
+
+    def __init__(self, ch, n_classes, tile, keep='device'):
+        if keep not in ('device', 'host'):
+            raise ValueError("keep must be 'device' or 'host', got %r" % (keep,))
+        if ch not in (1, 3):
+            raise ValueError('ch must be 1 or 3, got %s' % ch)
+        self.ch, self.n_classes, self.tile, self.keep = int(ch), _check_n_classes(n_classes), int(tile), keep
+        self._own = self                       # partitions share their parent's storage
+        self._img, self._mask = [], []         # chunks; _storage() joins them
+        self._sums = np.zeros((0, 2, self.ch), np.int64)
+        self._hist = np.zeros((0, self.n_classes), np.int64)
+        self._lo, self._hi = 0.0, 1.0
+
+    # -- filling
+    def _append(self, img, mask, sums, hist):
+        if self._own is not self:
+            raise ValueError('a partition is a view: add to the tile set it came from')
+        n = img.shape[0]
+        if tuple(img.shape[1:]) != (self.ch, self.tile, self.tile):
+            raise ValueError('tiles %s do not fit a [n,%d,%d,%d] set' % (tuple(img.shape), self.ch, self.tile, self.tile))
+        if (mask is None) != (hist is None):
+            raise ValueError('mask tiles and class histograms come together')
+        if self._img and (mask is None) != (not self._mask):
+            raise ValueError('a tile set holds masks for all of its tiles or for none')
+        if mask is not None and tuple(mask.shape) != (n, self.tile, self.tile):
+            raise ValueError('mask tiles %s do not match the tiles %s' % (tuple(mask.shape), tuple(img.shape)))
+        sums = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, dtype=np.int64).reshape(n, 2, self.ch)
+        if hist is not None:
+            hist = np.asarray(hist.cpu() if torch.is_tensor(hist) else hist, dtype=np.int64).reshape(n, -1)
+            if hist.shape[1] == self.n_classes + 1:
+                if hist[:, -1].any():
+                    raise ValueError('%d mask pixels hold a class index >= n_classes=%d' % (int(hist[:, -1].sum()), self.n_classes))
+                hist = hist[:, :self.n_classes]
+            if hist.shape[1] != self.n_classes:
+                raise ValueError('histograms of %d bins in a set of %d classes' % (hist.shape[1], self.n_classes))
+            self._hist = np.concatenate([self._hist, hist])
+        self._sums = np.concatenate([self._sums, sums])
+
+        def hold(t):
+            if self.keep == 'device':
+                if not t.is_cuda:
+                    raise L.PylcError("keep='device' holds device tensors")
+                return t
+            p = _pinned(t.shape)
+            p.copy_(t)
+            return p
+        self._img.append(hold(img))
+        if mask is not None:
+            self._mask.append(hold(mask))
+        return self
+
+    def add(self, extracted):
+        """Append extract_photo's tiles and statistics."""
+        if extracted.tile != self.tile:
+            raise ValueError('tiles of %d in a set of %d' % (extracted.tile, self.tile))
+        if extracted.mask is not None and extracted.n_classes != self.n_classes:
+            raise ValueError('tiles of %s classes in a set of %d' % (extracted.n_classes, self.n_classes))
+        return self._append(extracted.img, extracted.mask, extracted.sums, extracted.hist)
+
+    def from_arrays(self, img, mask=None, sums=None, hist=None, device='cuda'):
+        """Append existing tiles (uint8 [n,C,t,t], masks uint8 [n,t,t]; numpy or tensors, host or device).  Their statistics are computed
+        on the device by pylc_tile_stats unless given (sums int [n,2,C], hist int [n, n_classes])."""
+        img = torch.as_tensor(img)
+        mask = torch.as_tensor(mask) if mask is not None else None
+        if sums is None:
+            d_img = img.to(device)
+            d_mask = mask.to(device) if mask is not None else None
+            sums, hist = tile_stats(d_img, d_mask, self.n_classes)
+            if self.keep == 'device':
+                img, mask = d_img, d_mask
+        elif self.keep == 'device':
+            img, mask = img.to(device), (mask.to(device) if mask is not None else None)
+        return self._append(img.contiguous(), mask.contiguous() if mask is not None else None, sums, hist)
+
+    # -- access
+    def _storage(self):
+        own = self._own
+        for name in ('_img', '_mask'):
+            chunks = getattr(own, name)
+            if len(chunks) > 1:
+                if own.keep == 'device':
+                    joined = torch.cat(chunks)
+                else:
+                    joined = _pinned((sum(c.shape[0] for c in chunks),) + tuple(chunks[0].shape[1:]))
+                    torch.cat(chunks, out=joined)
+                setattr(own, name, [joined])
+        return (own._img[0] if own._img else None), (own._mask[0] if own._mask else None)
+
+    @property
+    def start(self):
+        return int(math.ceil(self._lo * self._own._sums.shape[0]))          # db/database.py:89-90
+
+    @property
+    def end(self):
+        return int(math.ceil(self._hi * self._own._sums.shape[0]))
+
+    def __len__(self):
+        return self.end - self.start
+
+    @property
+    def img(self):
+        t = self._storage()[0]
+        return None if t is None else t[self.start:self.end]
+
+    @property
+    def mask(self):
+        t = self._storage()[1]
+        return None if t is None else t[self.start:self.end]
+
+    @property
+    def sums(self):
+        return self._own._sums[self.start:self.end]
+
+    @property
+    def hist(self):
+        return self._own._hist[self.start:self.end] if self._own._mask else None
+
+    def coshuffle(self, seed):
+        """One np.random.RandomState(seed).permutation applied to images, masks and statistics alike (coshuffle, utils/tools.py:361-385,
+        seeded).  Partitions taken before see the new order."""
+        if self._own is not self:
+            raise ValueError('a partition is a view: shuffle the tile set it came from')
+        n = self._sums.shape[0]
+        perm = np.random.RandomState(seed).permutation(n)
+        img, mask = self._storage()
+        idx = torch.from_numpy(perm)
+
+        def take(t):
+            if t is None:
+                return []
+            if self.keep == 'device':
+                return [t.index_select(0, idx.to(t.device))]
+            out = _pinned(t.shape)
+            torch.index_select(t, 0, idx, out=out)
+            return [out]
+        self._img, self._mask = take(img), take(mask)
+        self._sums = self._sums[perm]
+        if self._hist.shape[0] == n:
+            self._hist = self._hist[perm]
+        return self
+
+    def partition(self, lo, hi):
+        """The tiles ceil(lo * n) .. ceil(hi * n) - 1 as a view (MLPDataset(partition=(0, 0.8)), db/database.py:89-91)."""
+        if not 0 <= lo <= hi <= 1:
+            raise ValueError('partition (%s, %s) outside 0 <= lo <= hi <= 1' % (lo, hi))
+        view = object.__new__(TileSet)
+        view.ch, view.n_classes, view.tile, view.keep = self.ch, self.n_classes, self.tile, self.keep
+        view._own = self._own
+        span = self._hi - self._lo
+        view._lo, view._hi = self._lo + lo * span, self._lo + hi * span
+        return view
+
+    def batches(self, batch_size, drop_last=True):
+        """A re-iterable of (img uint8 [B,C,t,t], mask uint8 [B,t,t] or None): device tensors gathered by index (keep='device', what
+        Model.train takes as is), or host arrays out of the pinned store (keep='host', what data.TileFeeder takes)."""
+        return _Batches(self, batch_size, drop_last)
+
+    def profile(self):
+        """The reference's dataset profile (profile_from_sums) of these tiles, as a dict under its meta names: Meta.update(profile) picks
+        up px_mean, px_std and weights.  Note px_std: the mean over tiles of the per-tile std, not the dataset's."""
+        if self.hist is None:
+            raise ValueError('a profile needs masks')
+        return profile_from_sums(self.sums, self.hist, self.tile, self.n_classes)
