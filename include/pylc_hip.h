@@ -624,6 +624,21 @@ int pylc_extract_tiles(const unsigned char* img, int Cimg, int H, int W, const u
  * or [n][tile][tile]; sums [n][2][Cimg], hist [n][n_classes + 1], zeroed by the caller. */
 int pylc_tile_stats(const unsigned char* img_tiles, long long n_tiles, int Cimg, int tile, const unsigned char* mask_tiles,
                     int n_classes, int band_rows, unsigned long long* sums, unsigned long long* hist, void* stream);
+/* The augmentation transform of `pylc.py augment` (augment_transform, utils/tools.py:452-594; csrc/augment.hip) on tiles that are
+ * on the device: copy k (k < m) is tile src_index[k] of img_tiles [n_src][Cimg][tile][tile] (and of mask_tiles [n_src][tile][tile],
+ * class indices, when given) warped by cv2.warpPerspective's arithmetic with the INVERSE matrix minv[k] (row-major 3 x 3, double:
+ * linear for the image, nearest for the mask, BORDER_REFLECT_101), cropped by 30 pixels on every side, resized back to the tile
+ * by cv2.resize's area-mode linear kernel (image) and nearest (mask), truncated, shifted by shift[k] and clipped to 0..255.  Every
+ * step is fixed to the bit (the definition: DESIGN.md section 5.6); the entry point takes the matrices and does not draw them.
+ * out_img [m][Cimg][tile][tile]; out_mask [m][tile][tile] or NULL.  sums [m][2][Cimg] and hist [m][n_classes + 1] follow
+ * pylc_extract_tiles' convention (added into buffers the caller zeroed; the last bin counts values >= n_classes); either may be NULL.
+ * All of img_tiles .. shift are device buffers.  128 <= tile <= 1024, Cimg 1 or 3, band_rows (output rows per block, 0 for the
+ * default) * tile <= 65536 and never changes a result; out_mask or hist without mask_tiles: PYLC_ERR_ARG, nothing is launched.
+ * src_index is read on the device: a copy whose entry lies outside 0 .. n_src - 1 is the caller's error and is left unwritten. */
+int pylc_augment_tiles(const unsigned char* img_tiles, const unsigned char* mask_tiles, long long n_src, int Cimg, int tile,
+                       const int* src_index, const double* minv, const int* shift, long long m, int band_rows,
+                       unsigned char* out_img, unsigned char* out_mask, int n_classes, unsigned long long* sums,
+                       unsigned long long* hist, void* stream);
 
 /* Confusion matrix cm[t*C + p] += 1 over n pixels of class-index masks (uint8 or int64; *_bytes = 1 or 8); the scores of
  * utils/metrics.py:64-88 (weighted F1, weighted IoU = the "mIoU", MCC, normalised matrix) are functions of it.

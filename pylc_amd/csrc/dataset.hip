@@ -19,15 +19,12 @@
 // (v_alignbyte).  Every dword it touches holds at least one byte of the row, so it lies in the same page as that byte.  The store is one
 // 16-byte store when the destination is aligned (always when tile % 16 == 0).  The last group of a row whose tile is no multiple of 16,
 // and stores to unaligned rows, go byte by byte.
-#include "common.h"
+#include "tile_bytes.h"
 
 namespace pylc {
 
 namespace {
 
-constexpr int kDsThreads = 256;
-constexpr int kDsBins = PYLC_MAX_CLASSES + 1;
-constexpr int kDsBandPixels = 65536;           // pixels per plane and block: 65 536 * 255^2 < 2^32
 constexpr int kDsAutoBandPixels = 8192;        // the default band: 16 rows of a 512 tile, 32 KB of RGB + mask per block
 
 struct TileGeom {
@@ -69,24 +66,6 @@ __device__ __forceinline__ uint4 load_group(const unsigned char* p, int valid) {
     return v;
 }
 
-__device__ __forceinline__ void store_group(unsigned char* p, const uint4& v, int valid) {
-    if (valid == 16 && ((unsigned long long)p & 15u) == 0) {
-        *reinterpret_cast<uint4*>(p) = v;
-    } else {
-        const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if (k < valid) p[k] = (unsigned char)(w[k >> 2] >> (8 * (k & 3)));
-    }
-}
-
-// the wave's total of v (it fits 32 bits: see kDsBandPixels) added to a 64-bit LDS accumulator
-__device__ __forceinline__ void wave_add(unsigned int v, unsigned long long* acc) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(acc, (unsigned long long)v);
-}
-
 // grid (n_tiles, bands); img_tiles [n][C][t][t] and mask_tiles [n][t][t] may be NULL (statistics only); sums [n][2][C] (sum x, then
 // sum x^2), hist [n][n_classes + 1] (the last bin: every value >= n_classes), both zeroed by the caller and indexed from this launch's
 // first tile.
@@ -120,12 +99,7 @@ __global__ __launch_bounds__(kDsThreads) void tile_cut_stats_kernel(TileGeom g, 
                 const int valid = t - x0 < 16 ? t - x0 : 16;
                 const uint4 v = load_group(src + (long long)r * g.pitch + x0, valid);
                 if (dst) store_group(dst + (long long)r * t + x0, v, valid);
-                const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    s[c] = __builtin_amdgcn_sad_u8(w[k], 0u, s[c]);            // + the four bytes
-                    ss[c] = __builtin_amdgcn_udot4(w[k], w[k], ss[c], false);  // + their squares
-                }
+                sum_group(v, s[c], ss[c]);
             }
         }
     }
@@ -138,32 +112,11 @@ __global__ __launch_bounds__(kDsThreads) void tile_cut_stats_kernel(TileGeom g, 
             const int valid = t - x0 < 16 ? t - x0 : 16;
             const uint4 v = load_group(src + (long long)r * g.pitch + x0, valid);
             if (dst) store_group(dst + (long long)r * t + x0, v, valid);
-            const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                if (k < valid) {
-                    const unsigned int b = (w[k >> 2] >> (8 * (k & 3))) & 255u;
-                    atomicAdd(&cnt[(b < top ? b : top) * kDsThreads + tid], 1u);
-                }
-            }
+            count_group(v, valid, top, cnt);
         }
     }
     __syncthreads();                                       // acc is zero everywhere
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (c < g.C) {
-            wave_add(s[c], &acc[c]);
-            wave_add(ss[c], &acc[3 + c]);
-        }
-    }
-    for (int b = 0; b < bins; ++b) wave_add(cnt[b * kDsThreads + tid], &acc[6 + b]);
-    __syncthreads();
-    if (tid < 6) {
-        const int which = tid / 3, c = tid - 3 * which;
-        if (c < g.C && acc[tid]) atomicAdd(&sums[(n * 2 + which) * g.C + c], acc[tid]);
-    } else if (tid < 6 + bins) {
-        if (acc[tid]) atomicAdd(&hist[n * bins + (tid - 6)], acc[tid]);
-    }
+    commit_tile_stats(s, ss, cnt, acc, g.C, bins, n, sums, hist);
 }
 
 int launch(const TileGeom& g0, int n_tiles, int band_rows, unsigned char* img_tiles, unsigned char* mask_tiles, unsigned long long* sums,

@@ -14,7 +14,11 @@ resize, since a nearest resize only selects pixels), step 3 is pylc_extract_tile
 the profile is made of (sum x, sum x^2 per channel, the class histogram); step 4 is double arithmetic on those exact integers on the host.
 A TileSet keeps the tiles on the device (or in pinned host memory) and hands Model.train its batches.
 
-Out of scope: the augmentation transform itself (perspective_shift, utils/tools.py:557-594), HDF5 files, file collation, print_meta."""
+The augmented copies those rates ask for (Augmentor.oversample -> augment_transform, utils/augment.py:184-239, utils/tools.py:452-594)
+are made by pylc_augment_tiles: augment_params draws a copy's warp and brightness shift as the reference does, augment_tiles applies them
+on the device, TileSet.oversample composes the class-balanced set.
+
+Out of scope: HDF5 files, file collation, print_meta."""
 import math
 
 import numpy as np
@@ -96,6 +100,96 @@ def tile_stats(img, mask=None, n_classes=None, band_rows=0):
         hist = torch.zeros((n, (n_classes or 0) + 1), device=img.device, dtype=torch.int64)
     check(lib.pylc_tile_stats(ptr(img), n, c, t, ptr(mask), n_classes or 0, band_rows, ptr(sums), ptr(hist), stream()))
     return sums, hist
+
+
+# ---- the augmentation transform ----------------------------------------------------------------------------------------------------
+AUG_MIN_TILE = 128
+_AUG_PTS = ((56, 65), (368, 52), (28, 387), (389, 390))         # perspective_shift's source points: fixed, whatever the tile
+
+
+def augment_params(j, tile):
+    """What augment_transform(img, mask, np.random.RandomState(j)) draws for a tile of side `tile`, in its order: the four points of
+    perspective_shift (utils/tools.py:580-584) and channel_shift's brightness shift (:549).  Returns (minv, shift): minv float64 [3,3],
+    the inverse of cv2.getPerspectiveTransform(pts1, pts2) -- what cv2.warpPerspective maps output pixels back with --, and the int shift.
+    The seed is the copy's index j alone: copy j of every tile gets the same warp, as in the reference."""
+    if tile < AUG_MIN_TILE:
+        raise ValueError('tile %d is below %d: the transform crops 30 pixels on every side' % (tile, AUG_MIN_TILE))
+    rs = np.random.RandomState(int(j))
+    alpha = 0.06 * tile
+    pts1 = np.float32(_AUG_PTS)
+    pts2 = pts1 + rs.uniform(-alpha, alpha, size=pts1.shape).astype(np.float32)
+    shift = int(rs.uniform(10, 20))
+    a = np.zeros((8, 8))
+    b = np.zeros(8)
+    for i in range(4):                                     # getPerspectiveTransform's system, solved in double
+        x, y, X, Y = float(pts1[i, 0]), float(pts1[i, 1]), float(pts2[i, 0]), float(pts2[i, 1])
+        a[i] = (x, y, 1, 0, 0, 0, -x * X, -y * X)
+        a[i + 4] = (0, 0, 0, x, y, 1, -x * Y, -y * Y)
+        b[i], b[i + 4] = X, Y
+    m = np.append(np.linalg.solve(a, b), 1.0).reshape(3, 3)
+    return np.linalg.inv(m), shift
+
+
+def warp_tiles(img, mask, src_index, minv, shift, n_classes=None, band_rows=0, stats=True):
+    """pylc_augment_tiles with the matrices given: copy k is tile src_index[k] of the device uint8 tiles img [n,C,t,t] (and of the class-index
+    masks [n,t,t], or None) under the inverse matrix minv[k] (float64 [m,3,3]) and the brightness shift[k].  Returns (img uint8 [m,C,t,t],
+    mask uint8 [m,t,t] or None, sums int64 [m,2,C], hist int64 [m, n_classes + 1] or None when there is no mask or no n_classes); sums and
+    hist are None with stats=False.  band_rows changes the launch only, never the result."""
+    L.init()
+    img = _u8(img, 'tiles')
+    if img.dim() != 4 or img.shape[2] != img.shape[3]:
+        raise ValueError('tiles must be [n,C,t,t], got %s' % (tuple(img.shape),))
+    n, c, t = img.shape[0], img.shape[1], img.shape[2]
+    src = np.asarray(src_index, dtype=np.int64).reshape(-1)
+    m = src.shape[0]
+    if m and (src.min() < 0 or src.max() >= n):
+        raise ValueError('src_index outside 0..%d' % (n - 1))
+    minv = np.ascontiguousarray(np.asarray(minv, dtype=np.float64).reshape(-1, 3, 3))
+    shift = np.asarray(shift, dtype=np.int64).reshape(-1)
+    if minv.shape[0] != m or shift.shape[0] != m:
+        raise ValueError('%d source indices, %d matrices, %d shifts' % (m, minv.shape[0], shift.shape[0]))
+    dev = img.device
+    if mask is not None:
+        mask = _u8(mask, 'mask tiles')
+        if tuple(mask.shape) != (n, t, t):
+            raise ValueError('mask tiles %s do not match the tiles %s' % (tuple(mask.shape), tuple(img.shape)))
+    d_src = torch.from_numpy(src.astype(np.int32)).to(dev)
+    d_minv = torch.from_numpy(minv).to(dev)
+    d_shift = torch.from_numpy(shift.astype(np.int32)).to(dev)
+    out = torch.empty((m, c, t, t), device=dev, dtype=torch.uint8)
+    mout = torch.empty((m, t, t), device=dev, dtype=torch.uint8) if mask is not None else None
+    sums = torch.zeros((m, 2, c), device=dev, dtype=torch.int64) if stats else None
+    hist = None
+    if stats and mask is not None and n_classes is not None:
+        hist = torch.zeros((m, n_classes + 1), device=dev, dtype=torch.int64)
+    check(lib.pylc_augment_tiles(ptr(img), ptr(mask), n, c, t, ptr(d_src), ptr(d_minv), ptr(d_shift), m, band_rows, ptr(out), ptr(mout),
+                                 n_classes or 0, ptr(sums), ptr(hist), stream()))
+    return out, mout, sums, hist
+
+
+def augment_tiles(img, mask, src_index, copy_index, band_rows=0, n_classes=None):
+    """The reference's augment_transform(tile src_index[k], RandomState(copy_index[k])) for every k, on the device: augment_params, then
+    warp_tiles (whose returns these are)."""
+    copy = np.asarray(copy_index, dtype=np.int64).reshape(-1)
+    tile = int(img.shape[-1])
+    params = {int(j): augment_params(int(j), tile) for j in np.unique(copy)}
+    minv = np.stack([params[int(j)][0] for j in copy]) if copy.size else np.zeros((0, 3, 3))
+    shift = [params[int(j)][1] for j in copy]
+    return warp_tiles(img, mask, src_index, minv, shift, n_classes, band_rows)
+
+
+def oversample_layout(rates):
+    """Augmentor.oversample's order before its shuffle (utils/augment.py:206-232): every tile i, followed by its copies j = 0 ..
+    rates[i] - 1.  Returns (src, copy), int64 [n + sum(rates)]: the tile each entry comes from and its copy index, -1 for the original."""
+    rates = np.asarray(rates)
+    if rates.size == 0:
+        rates = rates.astype(np.int64)
+    if rates.ndim != 1 or (rates.size and (not np.issubdtype(rates.dtype, np.integer) or rates.min() < 0)):
+        raise ValueError('rates must be a list of non-negative integers, one per tile')
+    src = np.repeat(np.arange(rates.size, dtype=np.int64), rates + 1)
+    first = np.cumsum(rates + 1) - (rates + 1)
+    copy = np.arange(src.size, dtype=np.int64) - first[src] - 1
+    return src, copy
 
 
 class Extracted:
@@ -459,6 +553,40 @@ class TileSet:
         """A re-iterable of (img uint8 [B,C,t,t], mask uint8 [B,t,t] or None): device tensors gathered by index (keep='device', what
         Model.train takes as is), or host arrays out of the pinned store (keep='host', what data.TileFeeder takes)."""
         return _Batches(self, batch_size, drop_last)
+
+    def oversample(self, rates, chunk=64, device='cuda'):
+        """Augmentor.oversample (utils/augment.py:184-239) without its shuffle: a NEW tile set of the same keep mode that holds, for every
+        tile i in order, the tile followed by rates[i] augmented copies (augment_tiles with copy indices 0 .. rates[i] - 1; rates as
+        oversample_rates returns them).  The originals carry their statistics over; the copies' are computed on the device by the launch
+        that makes them.  `chunk` source tiles are worked on at a time (a host set uploads them to `device`), so that the temporaries stay at
+        chunk * (1 + max(rates)) tiles.  Follow with coshuffle(seed) and profile().
+        ValueError: len(rates) != len(self), a set without masks, a copy with a class index >= n_classes."""
+        src, copy = oversample_layout(rates)
+        n = len(self)
+        if len(rates) != n:
+            raise ValueError('%d rates for %d tiles' % (len(rates), n))
+        if self.hist is None:
+            raise ValueError('oversampling needs masks: the rates come from their class histograms')
+        if chunk <= 0:
+            raise ValueError('chunk=%s' % chunk)
+        out = TileSet(self.ch, self.n_classes, self.tile, self.keep)
+        img, mask = self.img, self.mask
+        for lo in range(0, n, chunk):
+            hi = min(lo + chunk, n)
+            sel = (src >= lo) & (src < hi)
+            c_src, c_copy = src[sel] - lo, copy[sel]
+            aug = c_copy >= 0
+            d_img, d_mask = img[lo:hi], mask[lo:hi]
+            if self.keep == 'host':
+                d_img, d_mask = d_img.to(device, non_blocking=True), d_mask.to(device, non_blocking=True)
+            a_img, a_mask, a_sums, a_hist = augment_tiles(d_img, d_mask, c_src[aug], c_copy[aug], n_classes=self.n_classes)
+            # entry k of the chunk: original c_src[k], or the next copy in launch order
+            pick = np.where(aug, (hi - lo) + np.cumsum(aug) - 1, c_src)
+            idx = torch.from_numpy(pick).to(a_img.device)
+            sums = np.concatenate([self.sums[lo:hi], a_sums.cpu().numpy()])[pick]
+            hist = np.concatenate([np.pad(self.hist[lo:hi], ((0, 0), (0, 1))), a_hist.cpu().numpy()])[pick]
+            out._append(torch.cat([d_img, a_img]).index_select(0, idx), torch.cat([d_mask, a_mask]).index_select(0, idx), sums, hist)
+        return out
 
     def profile(self):
         """The reference's dataset profile (profile_from_sums) of these tiles, as a dict under its meta names: Meta.update(profile) picks
