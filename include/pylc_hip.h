@@ -646,6 +646,17 @@ int pylc_augment_tiles(const unsigned char* img_tiles, const unsigned char* mask
  * zeroed by the caller; integer atomics make the result exact and order-independent. */
 int pylc_confusion_matrix(const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C,
                           int force_coverage, unsigned long long* cm, void* stream);
+/* The same counts straight from a network's logits, with the argmax fused in (csrc/score.hip): logits are N pixel
+ * rows of `pitch` floats (pitch >= C, C in 2..PYLC_MAX_CLASSES; the NHWC tensor a net returns), read with 16-byte loads when pitch % 4 == 0
+ * and the base is 16-byte aligned, else float by float.  The class of a pixel is its FIRST maximum (strict `>` scan, numpy's argmax; NaN
+ * logits are not a supported input).  mask: NULL, or uint8 [N] receiving the class of every pixel (any alignment).  counts: NULL, or
+ * [C*C + 1]: counts[t*C + p] += 1 for every pixel whose target t lies in 0..C-1, counts[C*C] += 1 for every other pixel (tallied, never
+ * dropped).  The kernel ADDS into counts -- the caller zeroes it once and may launch many times into it --, with integer atomics only:
+ * exact, and independent of arrival order.  target: NULL (target_bytes 0), uint8 (1) or int64 (8) class indices [N]; read only with counts.
+ * mask and counts both NULL, counts without target, target and target_bytes disagreeing, a target_bytes other than 0 / 1 / 8, C or pitch
+ * out of range, N <= 0 or N > 2^39 (the bound of a block's 32-bit counters): PYLC_ERR_ARG, nothing is launched. */
+int pylc_logits_score(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
+                      unsigned long long* counts, void* stream);
 
 /* The general form: ((x - mean[c]) / std[c]) / denom on float (is_u8 = 0) or uint8 (is_u8 = 1) tiles.  denom = 255 is
  * pylc_image_pack[_u8]; denom = 1 is the reference's grayscale `default=True` branch, which omits the division by 255

@@ -155,4 +155,10 @@ def load_into(model, path, resume=False):
             adamw_state_from_torch(model.optim, data['optim'])
         import os
         model.loss.load(os.path.join(os.path.dirname(os.path.abspath(path)), 'losses.pth'), resume=True)      # loss.py:253-268: the loss log resumes too
+        spath = os.path.join(os.path.dirname(os.path.abspath(path)), 'scores.json')
+        if os.path.exists(spath):             # a run that scored its validation passes (trainer(score=True)) goes on scoring them
+            if getattr(model, 'scores', None) is None:
+                from .metrics import ScoreLog
+                model.scores = ScoreLog(model.meta.n_classes)
+            model.scores.load(spath)
     return data

@@ -1,0 +1,213 @@
+// Validation scores: from the network's NHWC logits straight to class bytes and confusion counts, in one pass.
+//
+// What a validation pass otherwise needs for the same matrix is an argmax that writes an int64 mask (8 B per pixel out, 8 B back in) and
+// pylc_confusion_matrix on it: two launches and 16 extra bytes per pixel.  Here a pixel's logits are read once, its class is the FIRST
+// maximum (the strict `>` scan of stitch_argmax_kernel, numpy's argmax), and cell target * C + class of an integer matrix is counted --
+// exact, and independent of the order in which pixels arrive.
+//
+// Geometry: a lane takes 4 consecutive pixels (one dword of the class mask wherever that dword is aligned), a block of 256 lanes 1024,
+// and at most SCORE_GRID blocks walk the pixels in a grid-stride loop.  With one block per CU there is one wave per SIMD, so the loads of
+// the NEXT round are issued before the current round is worked on (two register sets, ping-pong): the memory pipe stays busy while the
+// wave compares and counts.
+//
+// Counting: 32-bit counters in LDS, one 64-bit global atomic per non-zero cell per block (as confusion_kernel).  Masks are blobs, so the
+// 256 pixels of a wave's round mostly share one or two cells and one LDS atomic per pixel would serialise on them (section 5.6 has the same
+// finding for the tile histogram).  Each wave therefore first reduces in registers: the cell of the first lane that still holds one is
+// broadcast, a ballot per pixel slot finds every pixel of the wave with that cell, the leader adds the population count, those pixels
+// retire.  SCORE_ROUNDS such rounds clear a blob mask; what is left after them (uniformly random cells: ~80 distinct ones) goes to LDS with
+// one atomic per pixel, where it hardly collides.  Either way every pixel is added exactly once.
+#include "common.h"
+
+namespace pylc {
+
+constexpr int SCORE_MAXC = PYLC_MAX_CLASSES;
+constexpr int SCORE_GRID = kNumCU;         // blocks at most: one per CU, 262144 pixels per round of the grid
+constexpr int SCORE_ROUNDS = 4;            // wave-level rounds before the per-pixel LDS atomics
+// One block counts at most 1024 * ceil(ceil((N + 3) / 4) / (256 * SCORE_GRID)) pixels into its 32-bit LDS counters: below 2^32 for every
+// N <= 2^39, which the entry point checks (2^39 pixels of logits are 2 TiB at the smallest pitch).
+constexpr long long SCORE_MAX_PIXELS = 1ll << 39;
+
+typedef float score_f4 __attribute__((ext_vector_type(4)));
+typedef float score_f2 __attribute__((ext_vector_type(2)));
+
+// the 4 pixels a lane works on: exactly C logits each (no pad lane is loaded: a dead destination register would be reused while its load
+// is still in flight and stall the loads behind it) and their targets
+template <int C, typename TT>
+struct ScorePixels {
+    float v[4][C];
+    TT t[4];
+};
+
+// the 4 pixels of group g: pixel 4 g - off + k.  Pixels outside 0 .. N-1 (the ends of a mask that starts `off` bytes past a dword, the
+// tail, a lane past the last group) load the nearest real pixel instead and are never counted or written.
+template <int C, typename TT, bool VEC, bool HAS_T>
+__device__ __forceinline__ void score_load(ScorePixels<C, TT>& px, const float* __restrict__ logits, int pitch, const TT* __restrict__ target,
+                                           long long N, long long first) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        long long q = first + k;
+        q = q < 0 ? 0 : (q < N ? q : N - 1);
+        const float* row = logits + q * pitch;
+        if constexpr (VEC) {                               // rows are 16-byte aligned: 16-byte loads, then what is left of C in one or two
+            constexpr int C4 = C / 4 * 4;
+#pragma unroll
+            for (int c = 0; c < C4; c += 4) {
+                const score_f4 f = *reinterpret_cast<const score_f4*>(row + c);
+                px.v[k][c] = f.x; px.v[k][c + 1] = f.y; px.v[k][c + 2] = f.z; px.v[k][c + 3] = f.w;
+            }
+            if constexpr (C - C4 >= 2) {
+                const score_f2 f = *reinterpret_cast<const score_f2*>(row + C4);
+                px.v[k][C4] = f.x; px.v[k][C4 + 1] = f.y;
+            }
+            if constexpr ((C - C4) % 2 == 1) px.v[k][C - 1] = row[C - 1];
+        } else {
+#pragma unroll
+            for (int c = 0; c < C; ++c) px.v[k][c] = row[c];
+        }
+        if constexpr (HAS_T) px.t[k] = target[q];
+    }
+}
+
+template <int C, typename TT, bool HAS_T>
+__device__ __forceinline__ void score_work(const ScorePixels<C, TT>& px, long long N, long long first, unsigned char* __restrict__ mask,
+                                           unsigned int* hist) {
+    int cls[4], cell[4];
+    bool ok[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int best = 0;
+        float bv = px.v[k][0];
+#pragma unroll
+        for (int c = 1; c < C; ++c) if (px.v[k][c] > bv) { bv = px.v[k][c]; best = c; }     // first maximum (np.argmax)
+        cls[k] = best;
+        ok[k] = first + k >= 0 && first + k < N;
+    }
+    if (mask) {
+        if (ok[0] && ok[3]) {        // mask + first is dword-aligned by the choice of `off`
+            *reinterpret_cast<unsigned int*>(mask + first) = (unsigned)cls[0] | (unsigned)cls[1] << 8 | (unsigned)cls[2] << 16 | (unsigned)cls[3] << 24;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (ok[k]) mask[first + k] = (unsigned char)cls[k];
+        }
+    }
+    if constexpr (!HAS_T) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned long long t = (unsigned long long)(long long)px.t[k];        // a negative int64 target is out of range too
+        cell[k] = !ok[k] ? -1 : (t < (unsigned long long)C ? (int)t * C + cls[k] : C * C);
+    }
+    // wave-level rounds: every lane of the wave is here (the caller's loop is wave-uniform), retired pixels hold -1
+    const int lane = threadIdx.x & 63;
+#pragma unroll 1
+    for (int r = 0; r < SCORE_ROUNDS; ++r) {
+        const int mine = cell[0] >= 0 ? cell[0] : cell[1] >= 0 ? cell[1] : cell[2] >= 0 ? cell[2] : cell[3];
+        const unsigned long long holders = __ballot(mine >= 0);
+        if (holders == 0) return;
+        const int leader = __ffsll((long long)holders) - 1;
+        const int lc = __builtin_amdgcn_readlane(mine, leader);
+        int n = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool same = cell[k] == lc;
+            n += __popcll(__ballot(same));
+            cell[k] = same ? -1 : cell[k];
+        }
+        if (lane == leader) atomicAdd(&hist[lc], (unsigned)n);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) if (cell[k] >= 0) atomicAdd(&hist[cell[k]], 1u);
+}
+
+// HAS_T: a target and counts are given (else mask only: TT is not used)
+template <int C, typename TT, bool VEC, bool HAS_T>
+__global__ __launch_bounds__(256) void logits_score_kernel(const float* __restrict__ logits, int pitch, const TT* __restrict__ target, long long N,
+                                                            int off, unsigned char* __restrict__ mask, unsigned long long* __restrict__ counts) {
+    __shared__ unsigned int hist[C * C + 1];
+    if constexpr (HAS_T) {
+        for (int i = threadIdx.x; i < C * C + 1; i += 256) hist[i] = 0;
+        __syncthreads();
+    }
+    const long long groups = (N + off + 3) >> 2;
+    const long long step = (long long)gridDim.x * 256;
+    const int lane = threadIdx.x & 63;
+    long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    // `g - lane` is the wave's first group: the loop conditions are the same for the 64 lanes of a wave
+    ScorePixels<C, TT> a, b;
+    // The next round's loads are issued unconditionally (a round past the end re-reads the last pixel: indices are clamped), so that the
+    // number of loads in flight is the same on every path and the waits in score_work count past them instead of draining them.
+    score_load<C, TT, VEC, HAS_T>(a, logits, pitch, target, N, 4 * g - off);
+    while (g - lane < groups) {
+        score_load<C, TT, VEC, HAS_T>(b, logits, pitch, target, N, 4 * (g + step) - off);
+        score_work<C, TT, HAS_T>(a, N, 4 * g - off, mask, hist);
+        g += step;
+        if (g - lane >= groups) break;
+        score_load<C, TT, VEC, HAS_T>(a, logits, pitch, target, N, 4 * (g + step) - off);
+        score_work<C, TT, HAS_T>(b, N, 4 * g - off, mask, hist);
+        g += step;
+    }
+    if constexpr (HAS_T) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < C * C + 1; i += 256)
+            if (hist[i]) atomicAdd(&counts[i], (unsigned long long)hist[i]);
+    }
+}
+
+template <int C, typename TT, bool HAS_T>
+static void score_launch(bool vec, int blocks, hipStream_t st, const float* logits, int pitch, const void* target, long long N, int off,
+                         unsigned char* mask, unsigned long long* counts) {
+    if (vec)
+        hipLaunchKernelGGL((logits_score_kernel<C, TT, true, HAS_T>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target),
+                           N, off, mask, counts);
+    else
+        hipLaunchKernelGGL((logits_score_kernel<C, TT, false, HAS_T>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target),
+                           N, off, mask, counts);
+}
+
+#define PYLC_SCORE_FOR_C(MACRO)                                                                                        \
+    switch (C) {                                                                                                       \
+        case 2: MACRO(2); break; case 3: MACRO(3); break; case 4: MACRO(4); break; case 5: MACRO(5); break;           \
+        case 6: MACRO(6); break; case 7: MACRO(7); break; case 8: MACRO(8); break; case 9: MACRO(9); break;           \
+        case 10: MACRO(10); break; case 11: MACRO(11); break; case 12: MACRO(12); break; case 13: MACRO(13); break;   \
+        case 14: MACRO(14); break; case 15: MACRO(15); break; case 16: MACRO(16); break;                              \
+        default: return fail(PYLC_ERR_ARG, "logits_score: n_classes=%d unsupported (2..%d)", C, SCORE_MAXC);          \
+    }
+
+}  // namespace pylc
+
+using namespace pylc;
+
+extern "C" int pylc_logits_score(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
+                                 unsigned long long* counts, void* stream) {
+    PYLC_REQUIRE(logits, "logits_score: logits is NULL");
+    PYLC_REQUIRE(mask || counts, "logits_score: mask and counts are both NULL, nothing to compute");
+    PYLC_REQUIRE(C >= 2 && C <= SCORE_MAXC, "logits_score: n_classes=%d unsupported (2..%d)", C, SCORE_MAXC);
+    PYLC_REQUIRE(pitch >= C, "logits_score: pitch=%d below n_classes=%d", pitch, C);
+    PYLC_REQUIRE(N > 0 && N <= SCORE_MAX_PIXELS, "logits_score: N=%lld outside 1..2^39 (the bound of the 32-bit block counters)", N);
+    PYLC_REQUIRE(target_bytes == 0 || target_bytes == 1 || target_bytes == 8, "logits_score: target_bytes=%d (0: none, 1: uint8, 8: int64)",
+                 target_bytes);
+    PYLC_REQUIRE((target != nullptr) == (target_bytes != 0), "logits_score: target and target_bytes=%d disagree", target_bytes);
+    PYLC_REQUIRE(!counts || target, "logits_score: counts without target");
+    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(logits) & 3) == 0 && (reinterpret_cast<uintptr_t>(counts) & 7) == 0 &&
+                 (target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0), "logits_score: a buffer is not aligned to its element");
+    const bool vec = pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+    const int off = mask ? (int)(reinterpret_cast<uintptr_t>(mask) & 3) : 0;      // groups of 4 pixels start where the mask's dwords do
+    const long long groups = (N + off + 3) >> 2;
+    const long long want = cdiv<long long>(groups, 256);
+    const int blocks = (int)(want < SCORE_GRID ? want : SCORE_GRID);
+    hipStream_t st = as_stream(stream);
+    if (!counts) {                                                                 // mask only: a target, if any, is not read
+#define LAUNCH_SC(CC) score_launch<CC, unsigned char, false>(vec, blocks, st, logits, pitch, nullptr, N, off, mask, nullptr)
+        PYLC_SCORE_FOR_C(LAUNCH_SC)
+#undef LAUNCH_SC
+    } else if (target_bytes == 8) {
+#define LAUNCH_SC(CC) score_launch<CC, long long, true>(vec, blocks, st, logits, pitch, target, N, off, mask, counts)
+        PYLC_SCORE_FOR_C(LAUNCH_SC)
+#undef LAUNCH_SC
+    } else {
+#define LAUNCH_SC(CC) score_launch<CC, unsigned char, true>(vec, blocks, st, logits, pitch, target, N, off, mask, counts)
+        PYLC_SCORE_FOR_C(LAUNCH_SC)
+#undef LAUNCH_SC
+    }
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}

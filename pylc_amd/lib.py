@@ -191,6 +191,7 @@ SIGNATURES = {
     'pylc_tile_stats': (_I, [_P, _LL, _I, _I, _P, _I, _I, _P, _P, _P]),
     'pylc_augment_tiles': (_I, [_P, _P, _LL, _I, _I, _P, _P, _P, _LL, _I, _P, _P, _I, _P, _P, _P]),
     'pylc_confusion_matrix': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P]),
+    'pylc_logits_score': (_I, [_P, _I, _P, _I, _LL, _I, _P, _P, _P]),
     'pylc_nhwc_to_nchw': (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     'pylc_nchw_to_nhwc': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'pylc_multiloss_workspace_floats': (_SZ, [_LL, _I]),

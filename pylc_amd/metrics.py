@@ -40,3 +40,121 @@ def scores(cm):
 def evaluate(y_true, y_pred, n_classes):
     """Evaluator.evaluate() (utils/evaluate.py:131-148) minus the plotting / report printing."""
     return scores(confusion_matrix(y_true, y_pred, n_classes, force_coverage=True))
+
+
+# ---- validation scores while training: logits -> counts in one launch (csrc/score.hip, DESIGN.md section 5.7) ---------------------------
+def logits_confusion(logits, target=None, counts=None, return_mask=False):
+    """Confusion counts (and / or the class mask) of a batch of logits [B,C,H,W] as a net returns them, in ONE launch and without a host
+    synchronisation: the class of a pixel is the first maximum of its logits (numpy's argmax).  target [B,H,W], uint8 or int64 class
+    indices: counts[t * C + p] += 1, and counts[C * C] counts the pixels whose target lies outside 0..C-1.  `counts` (int64 [C*C + 1],
+    device) is ADDED into; a zeroed one is allocated when none is passed.  Returns counts (None without a target), or (counts, mask) with
+    return_mask, mask uint8 [B,H,W]."""
+    from . import ops
+    L.init()
+    if logits.dim() != 4:
+        raise ValueError('expected [B,C,H,W] logits, got %s' % (tuple(logits.shape),))
+    b, c, h, w = logits.shape
+    n = b * h * w
+    if target is None and counts is not None:
+        raise ValueError('counts need a target')
+    if target is None and not return_mask:
+        raise ValueError('neither a target nor return_mask: nothing to compute')
+    x = ops.as_nhwc(logits)
+    pitch = ops.pitch_of(x)
+    tbytes = 0
+    if target is not None:
+        if target.dtype not in (torch.uint8, torch.int64):
+            raise TypeError('target must be uint8 or int64 class indices, got %s' % target.dtype)
+        if target.numel() != n:
+            raise ValueError('target %s does not match logits %s' % (tuple(target.shape), tuple(logits.shape)))
+        target = target.to(x.device, non_blocking=True).contiguous()
+        tbytes = target.element_size()
+        if counts is None:
+            counts = torch.zeros(c * c + 1, device=x.device, dtype=torch.int64)
+        elif counts.dtype != torch.int64 or counts.numel() != c * c + 1 or not counts.is_contiguous():
+            raise ValueError('counts must be a contiguous int64 tensor of %d entries' % (c * c + 1))
+    mask = torch.empty((b, h, w), device=x.device, dtype=torch.uint8) if return_mask else None
+    check(lib.pylc_logits_score(ptr(x), pitch, ptr(target), tbytes, n, c, ptr(mask), ptr(counts), stream()))
+    return (counts, mask) if return_mask else counts
+
+
+def per_class(cm):
+    """{'iou', 'f1', 'support'}: [C] arrays of a count matrix, with scores()'s zero-division rules (a class neither present nor predicted
+    scores 0); scores()'s 'iou' and 'f1' are their support-weighted means."""
+    cm = np.asarray(cm.cpu() if torch.is_tensor(cm) else cm, np.float64)
+    tp, support, predicted = np.diag(cm), cm.sum(1), cm.sum(0)
+    f1 = np.where(support + predicted > 0, 2 * tp / np.maximum(support + predicted, 1), 0.0)
+    iou = np.where(support + predicted - tp > 0, tp / np.maximum(support + predicted - tp, 1), 0.0)
+    return {'iou': iou, 'f1': f1, 'support': support}
+
+
+class ScoreLog:
+    """Validation scores next to the loss log: add() accumulates the confusion counts of every validation batch on the device (one launch,
+    no host read), close() turns them into one row per validation pass -- the only D2H copy -- and tracks the best weighted IoU."""
+
+    def __init__(self, n_classes):
+        self.n_classes = int(n_classes)
+        self.counts = None                 # int64 [C*C + 1], allocated where the first logits live
+        self.last_counts = None            # host int64 [C,C] of the last closed pass (summed over the group)
+        self.rows = []
+        self.best_iou, self.is_best = 0.0, False
+
+    def _zeros(self, device):
+        return torch.zeros(self.n_classes * self.n_classes + 1, device=device, dtype=torch.int64)
+
+    def add(self, logits, target):
+        if logits.shape[1] != self.n_classes:
+            raise ValueError('ScoreLog of %d classes got logits with %d' % (self.n_classes, logits.shape[1]))
+        if self.counts is None:
+            self.counts = self._zeros(logits.device)
+        logits_confusion(logits, target, counts=self.counts)
+
+    def close(self, it, epoch, group=None):
+        """End of a validation pass: the counts (summed over `group` when given -- a collective every rank must reach) become a row
+        {'iter', 'epoch', 'f1', 'iou', 'mcc', 'class_iou', 'class_f1', 'support'}; the device counts are zeroed for the next pass.
+        Returns the row, or None when no pixel was added."""
+        c = self.n_classes
+        if self.counts is None:
+            self.counts = self._zeros('cpu')           # a rank that saw no batch still takes part in the collective
+        if group is not None:
+            from .runtime import runtime
+            runtime.sync_all_reduce(self.counts, group)           # int64: carried by the torch group (the native communicator takes floats)
+        host = self.counts.to('cpu', copy=True)                    # the one D2H copy of a validation pass
+        self.counts.zero_()
+        outside = int(host[c * c])
+        if outside:
+            raise ValueError('%d validation targets lie outside 0..%d' % (outside, c - 1))
+        cm = host[:c * c].view(c, c).clone()
+        self.last_counts = cm
+        if int(cm.sum()) == 0:
+            self.is_best = False
+            return None
+        s, pc = scores(cm), per_class(cm)
+        row = {'iter': int(it), 'epoch': int(epoch), 'f1': s['f1'], 'iou': s['iou'], 'mcc': s['mcc'],
+               'class_iou': [float(v) for v in pc['iou']], 'class_f1': [float(v) for v in pc['f1']], 'support': [int(v) for v in pc['support']]}
+        self.rows.append(row)
+        self.is_best = row['iou'] > self.best_iou
+        if self.is_best:
+            self.best_iou = row['iou']
+        return row
+
+    def save(self, path):
+        import json
+        import os
+        tmp = path + '.tmp.%d' % os.getpid()
+        with open(tmp, 'w') as f:
+            json.dump({'n_classes': self.n_classes, 'best_iou': float(self.best_iou), 'rows': self.rows}, f)
+        os.replace(tmp, path)
+
+    def load(self, path):
+        """Take up rows and best_iou from a file written by save(); False when there is none."""
+        import json
+        import os
+        if not os.path.exists(path):
+            return False
+        with open(path) as f:
+            data = json.load(f)
+        if int(data['n_classes']) != self.n_classes:
+            raise ValueError('%s holds scores of %d classes, this log has %d' % (path, data['n_classes'], self.n_classes))
+        self.rows, self.best_iou, self.is_best = list(data['rows']), float(data['best_iou']), False
+        return True

@@ -154,7 +154,23 @@ class Model:
         self.iter = 0
         self.epoch = 0
         self._bucketer = None
+        self.scores = None                  # a metrics.ScoreLog: Model.eval also counts the confusion matrix, Model.log closes the pass
+        self._best_by = 'dice'
         self._ranges_checked = False        # eval / test: False until the first batch after a training step has re-measured the weight ranges
+
+    @property
+    def best_by(self):
+        """What `loss.is_best` (the best-model copy of Model.save) follows: 'dice', the validation Dice loss (the reference's rule), or
+        'iou', the weighted IoU of `scores`."""
+        return self._best_by
+
+    @best_by.setter
+    def best_by(self, rule):
+        if rule not in ('dice', 'iou'):
+            raise ValueError("best_by is 'dice' or 'iou', got %r" % (rule,))
+        if rule == 'iou' and self.scores is None:
+            raise ValueError("best_by='iou' needs Model.scores (a metrics.ScoreLog)")
+        self._best_by = rule
 
     def update_meta(self, params):
         self.meta.update(params)
@@ -266,6 +282,8 @@ class Model:
         with torch.no_grad():
             y_hat = self.net(x4)
             self.loss.push(self.crit.all_losses(y_hat, y)[1:4])
+            if self.scores is not None:
+                self.scores.add(y_hat, y)
         return [y_hat]
 
     def test(self, x):
@@ -274,6 +292,12 @@ class Model:
         x4 = self.pack_input(x, default=self.meta.normalize_default)
         with torch.no_grad():
             return [self.net(x4)]
+
+    def predict(self, x):
+        """uint8 class masks [B,H',W'] of a tile batch (U-Net: the cropped size): test()'s forward, then the first maximum of every pixel's
+        logits in one launch (csrc/score.hip)."""
+        from . import metrics
+        return metrics.logits_confusion(self.test(x)[0], return_mask=True)[1]
 
     def _refresh_for_inference(self):
         """Weight ranges / prepared filter planes for an eval-mode forward: re-measured unconditionally on the first batch after a training
@@ -285,7 +309,14 @@ class Model:
     def log(self):
         if runtime.sync_group is not None:
             ops.check_equal_shards()
-        self.loss.log(self.iter, self.net.training)
+        training = self.net.training
+        self.loss.log(self.iter, training)
+        if self._best_by == 'iou' and self.scores is None:
+            raise ValueError("best_by='iou' needs Model.scores (a metrics.ScoreLog)")
+        if not training and self.scores is not None:
+            self.scores.close(self.iter, self.epoch, runtime.sync_group)      # (every rank reaches log() from validate: one aligned collective)
+            if self._best_by == 'iou':
+                self.loss.is_best = self.scores.is_best
 
     def get_lr(self):
         return self.optim.lr
@@ -315,5 +346,7 @@ class Model:
                 checkpoint.save(self, tmp, best=best)
                 os.replace(tmp, path)
             self.loss.save(os.path.join(d, 'losses.pth'))          # model.py:389-392: Model.save also writes the loss log
+            if self.scores is not None:
+                self.scores.save(os.path.join(d, 'scores.json'))
         if runtime.sync_group is not None:
             parallel.barrier(runtime.sync_group)

@@ -31,8 +31,14 @@ def validate(model, batches, save_dir=None):
     return model
 
 
-def trainer(model, train_batches, valid_batches, n_epochs, save_dir=None):
-    """train.py:72-92, including its resume quirk `range(offset, n_epochs - offset)`."""
+def trainer(model, train_batches, valid_batches, n_epochs, save_dir=None, score=False, best_by='dice'):
+    """train.py:72-92, including its resume quirk `range(offset, n_epochs - offset)`.
+    score: every validation pass also logs weighted F1 / IoU / MCC and the per-class scores (metrics.ScoreLog -> scores.json next to
+    losses.pth); best_by: 'dice' (the reference's rule) or 'iou' (needs score) picks what the best-model copy follows."""
+    if score and model.scores is None:
+        from .metrics import ScoreLog
+        model.scores = ScoreLog(model.meta.n_classes)
+    model.best_by = best_by
     model.net.train()
     offset = model.epoch
     for epoch in range(offset, n_epochs - offset):
