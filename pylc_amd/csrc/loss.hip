@@ -156,6 +156,7 @@ extern "C" size_t pylc_multiloss_workspace_floats(long long N, int C) {
 
 extern "C" int pylc_multiloss_stats(const float* logits, int pitch, const int64_t* target, long long N, int C, const float* cw, float* stats,
                                     float* workspace, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats: n_classes=%d unsupported (2..%d)", C, MAXC);
     PYLC_REQUIRE(logits && target && stats && workspace && N > 0 && pitch >= C, "multiloss_stats: bad arguments");
     hipStream_t st = as_stream(stream);
     const int blocks = (int)(cdiv<long long>(N, 256) < kLossBlocks ? cdiv<long long>(N, 256) : kLossBlocks);
@@ -181,6 +182,7 @@ extern "C" int pylc_multiloss_finalize(const float* stats, double n_global, int 
 extern "C" int pylc_multiloss_bwd(const float* logits, int pitch, const int64_t* target, long long N, int C, const float* cw,
                                   const float* stats, double n_global, float w_ce, float w_dice, float w_focal, const float* grad_scale,
                                   float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd: n_classes=%d unsupported (2..%d)", C, MAXC);      // before amax_bits is cleared
     PYLC_REQUIRE(logits && target && stats && dlogits && N > 0 && pitch >= C && dpitch >= C && n_global > 0, "multiloss_bwd: bad arguments");
     hipStream_t st = as_stream(stream);
     if (amax_bits != nullptr) PYLC_HIP(hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st));

@@ -56,7 +56,14 @@ def _check(dev, rows, shape, target, c, pitch, lead=0):
     return got
 
 
-@pytest.mark.parametrize('c,pitch', [(2, 4), (9, 12), (11, 12), (16, 16)])
+# the four cases the file began with, then every other class count at pitch round4(C) (what a head writes), then a pitch one group of four wider
+# than the classes fill for every C % 4 == 0 (at pitch C those have no pad lane at all)
+SCORE_CASES = [(2, 4), (9, 12), (11, 12), (16, 16)]
+SCORE_CASES += [(c, (c + 3) & ~3) for c in range(2, 17) if (c, (c + 3) & ~3) not in SCORE_CASES]
+SCORE_CASES += [(c, c + 4) for c in range(4, 17, 4)]
+
+
+@pytest.mark.parametrize('c,pitch', SCORE_CASES)
 def test_counts_and_mask_match_numpy(dev, c, pitch):
     shape = (3, 37, 53)                                  # 5883 pixels: no multiple of 4, 64 or 256
     n = shape[0] * shape[1] * shape[2]
