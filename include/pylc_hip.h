@@ -482,6 +482,19 @@ int pylc_bn_bwd_apply_ex(const float* dout, int dout_pitch, const float* out, in
                          const float* mean, const float* invstd, const float* gamma, const float* sums, double n, long long M,
                          int C, int relu, float* dy, int dy_pitch, float* g_out, int g_pitch, unsigned int* amax_dy,
                          const float* scale, const float* shift, const PylcBnExtra* ex, void* stream);
+/* Backward of a FROZEN BatchNorm -- mean / invstd are constants (the running statistics: pylc_bn_eval_coeffs_full) -- in one pass:
+ *     g = [dropout mask * keep scale *] dout * (pre-activation > 0 if relu),   dy = gamma*invstd*g,   g_out = g (may be NULL),
+ *     sums[0:C] = sum g*xhat (= dgamma), sums[C:2C] = sum g (= dbeta), xhat = (y - mean)*invstd.
+ * 12 B per element (16 with g_out) where pylc_bn_bwd_reduce + pylc_bn_bwd_apply read dout and y twice (20 / 24); dy, g_out and sums are
+ * bit-identical to that pair run on zero sums (same slabs, same row order).  The ReLU mask comes from ex->relu_mask, else `out`, else
+ * y*scale + shift recomputed (no residual in the forward), as in pylc_bn_bwd_reduce.  sums == NULL (with workspace == NULL): neither
+ * parameter takes a gradient -- no reduction, and y is read only for a recomputed mask (it may be NULL otherwise).  workspace:
+ * pylc_bn_workspace_floats(M, C) floats.  amax_dy as in pylc_bn_bwd_apply.  ex (may be NULL): drop_p / drop_seed and relu_mask only --
+ * all operands are fp32 (any pitch, C % 4 == 0); a call with a plane field set is refused. */
+int pylc_bn_frozen_bwd(const float* dout, int dout_pitch, const float* out, int out_pitch, const float* y, int y_pitch,
+                       const float* mean, const float* invstd, const float* gamma, long long M, int C, int relu, float* dy,
+                       int dy_pitch, float* g_out, int g_pitch, unsigned int* amax_dy, const float* scale, const float* shift,
+                       float* sums /*[2C] or NULL*/, float* workspace, const PylcBnExtra* ex, void* stream);
 /* Plain ReLU forward / backward on [M][C] (Xception's stand-alone ReLUs, xception.py:83-84,199-232). */
 int pylc_relu_fwd(const float* x, int x_pitch, float* out, int out_pitch, long long M, int C, void* stream);
 int pylc_relu_bwd(const float* dout, int dout_pitch, const float* out, int out_pitch, float* dx, int dx_pitch,

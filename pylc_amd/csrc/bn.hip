@@ -573,6 +573,99 @@ __global__ __launch_bounds__(256, 3) void bn_bwd_apply_kernel(const float* __res
     if (amax_dy != nullptr) amax_commit(amax, amax_dy);
 }
 
+// Backward of a FROZEN BatchNorm (constant statistics: the running mean / variance of a loaded model) in ONE walk.  With mean and invstd
+// constants, dy = gamma invstd g does not depend on the sums, so what bn_reduce_kernel<1> and bn_bwd_apply_kernel do in two passes over
+// (dout, y) -- 20 B per element, 24 with the residual's gradient -- is one: read dout, y [, mask source], write dy [, g_out]: 12 / 16 B.
+// Same slab geometry, row batches (kRowBatch) and accumulation as bn_reduce_kernel<1>, same expression k * g as bn_bwd_apply_kernel on
+// zero sums: dy, g_out and [sum g xhat | sum g] are bit-identical to that pair.
+// SUMS == false (neither gamma nor beta takes a gradient): no reduction, no LDS; with MS_OUT / MS_BITS y is not read at all.
+template <bool SUMS, bool DROP, int MS>
+__global__ __launch_bounds__(256, 2) void bn_frozen_bwd_kernel(const float* __restrict__ dout, int dout_pitch,
+                                                               const float* __restrict__ out, int out_pitch,
+                                                               const float* __restrict__ y, int y_pitch,
+                                                               const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                               const float* __restrict__ gamma, int C, int relu,
+                                                               float* __restrict__ dy, int dy_pitch, float* __restrict__ g_out, int g_pitch,
+                                                               Slab g, unsigned* __restrict__ amax_dy, const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, float* __restrict__ partial,
+                                                               const unsigned char* __restrict__ mask, DropRef dr) {
+    __shared__ double red[SUMS ? 2 : 1][SUMS ? 4 : 1][SUMS ? 256 : 1];      // [sum][component][thread], as bn_reduce_kernel
+    const int tx = threadIdx.x % g.cols, ty = threadIdx.x / g.cols;
+    const long long r_begin = (long long)blockIdx.x * g.rows_per_slab;
+    long long r_end = r_begin + g.rows_per_slab;
+    if (r_end > g.M) r_end = g.M;
+    float amax = 0.f;
+    const bool remask = MS == MS_Y && relu;                      // ReLU mask recomputed from y (no residual in the forward)
+    constexpr bool NEED_Y = SUMS || MS == MS_Y;
+    for (int cb = 0; cb < g.CV; cb += g.cols) {
+        const int cv = cb + tx;
+        const bool active = ty < g.RL && cv < g.CV;
+        double d0[4] = {0.0, 0.0, 0.0, 0.0}, d1[4] = {0.0, 0.0, 0.0, 0.0};
+        if (active) {
+            f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};      // sums of the current batch of rows
+            const f32x4 is = ld4(invstd + 4 * cv);
+            const f32x4 k = ld4(gamma + 4 * cv) * is;
+            f32x4 mu = {0.f, 0.f, 0.f, 0.f}, sc = mu, sh = mu;
+            if constexpr (SUMS) mu = ld4(mean + 4 * cv);
+            if (remask) { sc = ld4(scale + 4 * cv); sh = ld4(shift + 4 * cv); }
+            f32x4 vg[kRowBatch], vy[kRowBatch], vo[MS == MS_OUT ? kRowBatch : 1];
+            unsigned vm[MS == MS_BITS ? kRowBatch : 1];
+            walk_rows(r_begin + ty, r_end, g.RL,
+                [&](int u, long long r) {
+                    vg[u] = ld4(dout + r * dout_pitch + 4 * cv);
+                    if constexpr (NEED_Y) { if (SUMS || remask) vy[u] = ld4(y + r * y_pitch + 4 * cv); }
+                    if constexpr (MS == MS_OUT) vo[u] = ld4(out + r * out_pitch + 4 * cv);
+                    if constexpr (MS == MS_BITS) vm[u] = mask[(r * g.CV + cv) >> 1];
+                },
+                [&](int u, long long r, bool valid) {
+                    f32x4 gg = vg[u];
+                    if constexpr (DROP) gg = drop4(dr, r, g.CV, cv, gg);
+                    if constexpr (MS == MS_Y) { if (remask) gg = relu_mask(gg, vy[u] * sc + sh); }      // the forward's own expression: identical bits
+                    if constexpr (MS == MS_OUT) gg = relu_mask(gg, vo[u]);
+                    if constexpr (MS == MS_BITS) gg = mask_apply(gg, vm[u], cv);
+                    if constexpr (SUMS) {
+                        const f32x4 xh = (vy[u] - mu) * is;
+                        if (valid) { s0 += gg; s1 += gg * xh; }
+                    }
+                    const f32x4 v = k * gg;
+                    vg[u] = gg;                                      // the masked gradient (residual branch) and dy, kept for the store pass
+                    vy[u] = v;
+                    if (valid) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+                },
+                [&](int u, long long r) {
+                    if (g_out != nullptr) st4(g_out + r * g_pitch + 4 * cv, vg[u]);
+                    st4(dy + r * dy_pitch + 4 * cv, vy[u]);
+                },
+                [&] {
+                    if constexpr (SUMS) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) { d0[j] += (double)s0[j]; d1[j] += (double)s1[j]; }
+                        s0 = f32x4{0.f, 0.f, 0.f, 0.f};
+                        s1 = s0;
+                    }
+                });
+        }
+        if constexpr (SUMS) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { red[0][j][threadIdx.x] = d0[j]; red[1][j][threadIdx.x] = d1[j]; }
+            __syncthreads();
+            if (ty == 0 && cv < g.CV) {
+                for (int l = 1; l < g.RL; ++l) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { d0[j] += red[0][j][l * g.cols + tx]; d1[j] += red[1][j][l * g.cols + tx]; }
+                }
+                const f32x4 f0 = {(float)d0[0], (float)d0[1], (float)d0[2], (float)d0[3]};
+                const f32x4 f1 = {(float)d1[0], (float)d1[1], (float)d1[2], (float)d1[3]};
+                float* p = partial + (size_t)blockIdx.x * 2 * C;
+                st4(p + 4 * cv, f1);             // [sum g*xhat (dgamma) | sum g (dbeta)]: the parameter order
+                st4(p + C + 4 * cv, f0);
+            }
+            __syncthreads();
+        }
+    }
+    if (amax_dy != nullptr) amax_commit(amax, amax_dy);
+}
+
 // Column combine of bn_reduce_kernel<1>'s partials (column_sum_kernel's arithmetic: fp64, fixed order) for BOTH halves of 8 channels
 // per block, plus the range bound of the dy that bn_bwd_apply is about to write as fp16 planes:
 //     dy = k (g - sg - xhat sgx),  k = gamma invstd  =>  |dy| <= |k| (max|g| + |sg| + sqrt(n - 1) |sgx|)       (|xhat| <= sqrt(n - 1))
@@ -1024,6 +1117,51 @@ extern "C" int pylc_bn_bwd_apply(const float* dout, int dout_pitch, const float*
                                  const float* scale, const float* shift, void* stream) {
     return pylc_bn_bwd_apply_ex(dout, dout_pitch, out, out_pitch, y, y_pitch, mean, invstd, gamma, sums, n, M, C, relu, dy, dy_pitch, g_out,
                                 g_pitch, amax_dy, scale, shift, nullptr, stream);
+}
+
+extern "C" int pylc_bn_frozen_bwd(const float* dout, int dout_pitch, const float* out, int out_pitch, const float* y, int y_pitch,
+                                  const float* mean, const float* invstd, const float* gamma, long long M, int C, int relu, float* dy,
+                                  int dy_pitch, float* g_out, int g_pitch, unsigned int* amax_dy, const float* scale, const float* shift,
+                                  float* sums, float* workspace, const PylcBnExtra* ex, void* stream) {
+    if (int rc = check_mc(M, C, dout_pitch, "bn_frozen_bwd")) return rc;
+    if (int rc = check_mc(M, C, dy_pitch, "bn_frozen_bwd(dy)")) return rc;
+    if (int rc = check_ex(ex, C, "bn_frozen_bwd")) return rc;
+    PYLC_REQUIRE(!ex || !(ex->out_planes || ex->res_planes || ex->dy_planes || ex->y_half_bound || ex->dout_half_bound || ex->g_amax),
+                 "bn_frozen_bwd: fp32 operands only (no fp16-plane fields of PylcBnExtra)");
+    PYLC_REQUIRE(dout && invstd && gamma && dy, "bn_frozen_bwd: null pointer");
+    PYLC_REQUIRE((sums == nullptr) == (workspace == nullptr), "bn_frozen_bwd: sums and workspace are given together (or neither: no sums)");
+    const unsigned char* mask = ex ? static_cast<const unsigned char*>(ex->relu_mask) : nullptr;
+    const int ms = !relu ? MS_Y : mask ? MS_BITS : out ? MS_OUT : MS_Y;
+    PYLC_REQUIRE(ms != MS_OUT || (out_pitch >= C && out_pitch % 4 == 0), "bn_frozen_bwd: bad out pitch");
+    PYLC_REQUIRE(!relu || ms != MS_Y || (scale && shift),
+                 "bn_frozen_bwd: relu needs `out`, the 1-bit mask, or scale and shift to recompute the mask from y");
+    const bool need_y = sums != nullptr || (relu && ms == MS_Y);
+    PYLC_REQUIRE(!need_y || (y && y_pitch >= C && y_pitch % 4 == 0), "bn_frozen_bwd: y (pitch %d) is needed for the sums / the ReLU mask", y_pitch);
+    PYLC_REQUIRE(sums == nullptr || mean, "bn_frozen_bwd: the sums need mean");
+    PYLC_REQUIRE(g_out == nullptr || (g_pitch >= C && g_pitch % 4 == 0), "bn_frozen_bwd: bad g pitch");
+    const bool drop = ex != nullptr && ex->drop_p > 0.f;
+    PYLC_REQUIRE(!(drop && ms == MS_BITS), "bn_frozen_bwd: the 1-bit ReLU mask and fused dropout are not combined");
+    const Slab g = make_slab(M, C);
+    hipStream_t st = as_stream(stream);
+    const BnEx bx = make_ex(ex);
+    const DropRef dr{bx.drop_thresh, bx.keep_scale, bx.seed};
+#define PYLC_BN_FROZEN(SUMSV, DROPV, MSV)                                                                                                 \
+    hipLaunchKernelGGL((bn_frozen_bwd_kernel<SUMSV, DROPV, MSV>), dim3(g.nslab), dim3(256), 0, st, dout, dout_pitch, out, out_pitch, y, y_pitch, mean, \
+                       invstd, gamma, C, relu, dy, dy_pitch, g_out, g_pitch, g, amax_dy, scale, shift, workspace, mask, dr)
+#define PYLC_BN_FROZEN_S(SUMSV)                                                                                                           \
+    { if (drop) { if (ms == MS_OUT) PYLC_BN_FROZEN(SUMSV, true, MS_OUT); else PYLC_BN_FROZEN(SUMSV, true, MS_Y); }                        \
+      else if (ms == MS_BITS) PYLC_BN_FROZEN(SUMSV, false, MS_BITS);                                                                      \
+      else if (ms == MS_OUT) PYLC_BN_FROZEN(SUMSV, false, MS_OUT);                                                                        \
+      else PYLC_BN_FROZEN(SUMSV, false, MS_Y); }
+    if (sums != nullptr) PYLC_BN_FROZEN_S(true) else PYLC_BN_FROZEN_S(false)
+#undef PYLC_BN_FROZEN_S
+#undef PYLC_BN_FROZEN
+    PYLC_LAUNCH_CHECK();
+    if (sums != nullptr) {
+        hipLaunchKernelGGL(column_sum_kernel, dim3(cdiv(2 * C, 8)), dim3(256), 0, st, workspace, g.nslab, 2 * C, sums);
+        PYLC_LAUNCH_CHECK();
+    }
+    return PYLC_OK;
 }
 
 extern "C" int pylc_relu_fwd(const float* x, int x_pitch, float* out, int out_pitch, long long M, int C, void* stream) {

@@ -17,6 +17,7 @@ class Conv2d(nn.Module):
         super().__init__()
         self.cin, self.cout, self.k = cin, cout, k
         self.feeds_bn = bn and cout % 4 == 0      # a BatchNorm consumes the output: emit its statistics from the conv epilogue
+        self.bn_frozen = False                    # ... unless that BatchNorm is frozen (BatchNorm2d.frozen): nobody reads them
         self.stride, self.padding, self.dilation = stride, padding, dilation
         w = torch.empty(cout, k, k, cin)
         fan_in = cin * k * k
@@ -33,7 +34,7 @@ class Conv2d(nn.Module):
             self.register_parameter('bias', None)
 
     def forward(self, x, res_link=None, out=None):
-        return ops.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.feeds_bn and self.training, res_link, out)
+        return ops.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.feeds_bn and self.training and not self.bn_frozen, res_link, out)
 
     def takes_planes(self):
         """Static part of ops.conv_takes_planes: a BatchNorm that feeds ONLY convs for which this holds may write fp16 planes."""
@@ -50,15 +51,23 @@ class DepthwiseConv3x3(nn.Module):
     def __init__(self, c, stride=1, dilation=1):
         super().__init__()
         self.c, self.stride, self.dilation = c, stride, dilation
+        self.bn_frozen = False      # as Conv2d.bn_frozen
         self.weight = nn.Parameter(torch.empty(c, 1, 3, 3).normal_(0, math.sqrt(2.0 / (9 * c))))
 
     def forward(self, x, res_link=None):
-        return ops.dwconv3x3(x, self.weight, self.stride, self.dilation, res_link, want_stats=self.training)     # always followed by a BatchNorm
+        return ops.dwconv3x3(x, self.weight, self.stride, self.dilation, res_link, want_stats=self.training and not self.bn_frozen)     # always followed by a BatchNorm
 
 
 class BatchNorm2d(nn.Module):
     """BatchNorm2d with the following ReLU / residual add fused into the same pass.  Synchronises its statistics
-    over runtime.sync_group when one is set (the RCCL replacement of models/sync_batchnorm)."""
+    over runtime.sync_group when one is set (the RCCL replacement of models/sync_batchnorm).
+
+    frozen (default False; not part of the state dict): in train() mode the module normalises with its RUNNING statistics as constants
+    (ops.bn_act(frozen=True)) -- gamma and beta still learn, the fused dropout still applies, running statistics and
+    num_batches_tracked stay as loaded, nothing is synchronised.  eval() mode is unchanged.  The conv in front of a frozen BatchNorm
+    should not emit statistics (Conv2d.bn_frozen); DeepLab.set_bn_frozen sets both."""
+
+    frozen = False
 
     def __init__(self, c, eps=1e-5, momentum=0.1):
         super().__init__()
@@ -77,6 +86,9 @@ class BatchNorm2d(nn.Module):
     def forward(self, y, residual=None, relu=False, res_link=None, out_planes=False, drop=None, into=None, sole=False, defer=False):
         """out_planes: every consumer of the output is a conv with takes_planes() (or a BatchNorm residual input) -- write fp16 planes.
         drop: the Dropout module that follows the activation in the reference, fused into this pass."""
+        if self.training and self.frozen:
+            return ops.bn_act(y, self.weight, self.bias, self.running_mean, self.running_var, residual, relu, True, self.eps, self.momentum,
+                              None, False, res_link, False, drop.spec() if drop is not None else None, into, frozen=True)
         if self.training:
             self._nbt_pending += 1          # no per-layer device add: 113 tiny launches per step otherwise
         return ops.bn_act(y, self.weight, self.bias, self.running_mean, self.running_var, residual, relu,
@@ -155,13 +167,14 @@ def bn_group(entries):
     Per layer the kernels and their order are exactly those of BatchNorm2d.forward."""
     specs = []
     for bn, y, kw in entries:
-        if bn.training:
+        frozen = bn.training and bn.frozen
+        if bn.training and not frozen:
             bn._nbt_pending += 1
         drop = kw.get('drop')
         specs.append(dict(y=y, gamma=bn.weight, beta=bn.bias, running_mean=bn.running_mean, running_var=bn.running_var, training=bn.training,
                           eps=bn.eps, momentum=bn.momentum, clamp_eps=runtime.bn_clamp_eps, residual=kw.get('residual'), relu=kw.get('relu', False),
                           res_link=kw.get('res_link'), out_planes=kw.get('out_planes', False), drop=drop.spec() if drop is not None else None,
-                          into=kw.get('into'), sole=kw.get('sole', False)))
+                          into=kw.get('into'), sole=kw.get('sole', False), frozen=frozen))
     training = entries[0][0].training
     return ops.bn_act_group(specs, runtime.sync_group if (training and runtime.sync_bn) else None)
 

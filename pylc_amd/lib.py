@@ -162,6 +162,7 @@ SIGNATURES = {
     'pylc_bn_apply': (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _LL, _I, _I, _P, _P]),
     'pylc_bn_bwd_reduce': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _LL, _I, _I, _P, _P, _P, _P, _P]),
     'pylc_bn_bwd_apply': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _D, _LL, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P]),
+    'pylc_bn_frozen_bwd': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _LL, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, C.POINTER(BnExtra), _P]),
     'pylc_relu_fwd': (_I, [_P, _I, _P, _I, _LL, _I, _P]),
     'pylc_relu_bwd': (_I, [_P, _I, _P, _I, _P, _I, _LL, _I, _P]),
     'pylc_maxpool_fwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

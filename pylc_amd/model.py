@@ -51,6 +51,7 @@ class Meta:
         self.pad_size = 94                 # (512 - 324) // 2, config.py:230; the valid-conv shrink is 188 px at any size
         self.report = 20                   # config.py:240
         self.pretrained = False
+        self.freeze_bn = False             # fine-tuning: BatchNorms keep their running statistics in training steps (DeepLab(freeze_bn=True))
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise AttributeError('unknown Meta field %r' % k)
@@ -180,9 +181,12 @@ class Model:
     def build(self):
         m = self.meta
         if m.arch == 'unet':
+            if m.freeze_bn:
+                raise ValueError('freeze_bn is not available for arch=unet: frozen BatchNorm is implemented for the DeepLab networks only '
+                                 '(the U-Net keeps batch statistics in its training kernels)')
             self.net = UNet(in_channels=m.ch, n_classes=m.n_classes, up_mode=m.up_mode, dropout=m.dropout)
         elif m.arch == 'deeplab':
-            self.net = DeepLab(backbone=m.backbone, n_classes=m.n_classes, in_channels=m.ch, pretrained=False)
+            self.net = DeepLab(backbone=m.backbone, n_classes=m.n_classes, in_channels=m.ch, freeze_bn=bool(m.freeze_bn), pretrained=False)
         else:
             raise ValueError('Model {} not available.'.format(m.arch))
         self.net = self.net.to(self.device)
@@ -239,6 +243,9 @@ class Model:
     def train(self, x, y):
         """One optimisation step (model.py:282-336)."""
         self.net.train()       # (parameter ranges / prepared filters are current: refreshed by every optimiser step and state load)
+        if getattr(self.net, 'freeze_bn', False) and ops.nplanes() == 1:
+            raise ValueError('freeze_bn is not available in conv precision mode 3: its half activations are scaled with range bounds '
+                             'taken from batch statistics, which a frozen BatchNorm does not compute')
         self._ranges_checked = False
         x4 = self.pack_input(x)
         y = self.crop_target(y.to(self.device, non_blocking=True).long())

@@ -43,7 +43,8 @@ class ASPP(nn.Module):
         # torch.cat (aspp.py:80) by slice: every branch's BatchNorm pass -- in inference the fused conv epilogue -- and the image-pool branch's
         # interpolation write their 256 channels straight into the 1280-channel buffer the projection conv reads
         buf = [ops.empty_nhwc(x.shape[0], 1280, h, w, x.device)]
-        if self.training and torch.is_grad_enabled() and runtime.sync_group is not None and runtime.sync_bn and runtime.coalesce_sync_bn:
+        if (self.training and torch.is_grad_enabled() and runtime.sync_group is not None and runtime.sync_bn and runtime.coalesce_sync_bn
+                and not self.bn1.frozen):         # (frozen BatchNorms exchange nothing: the plain branch)
             # SyncBN: the five branches are parallel, so their BatchNorms' statistics travel in ONE all-reduce per direction (10 -> 2
             # collectives per step): all five convs first, then the BatchNorms as one node (layers.bn_group)
             pool_conv, pool_bn = self.global_avg_pool.child(1), self.global_avg_pool.child(2)
@@ -99,7 +100,13 @@ class DeepLab(nn.Module):
     """DeepLab(activ_func=, normalizer=, backbone=, output_stride=16, n_classes=, in_channels=, freeze_bn=, pretrained=)
     -- the call made at models/model.py:166-173.  activ_func / normalizer are accepted for signature
     compatibility; the HIP path always runs ReLU and (Sync)BatchNorm, which is also all the reference can select
-    (SURVEY.md section 5 'Config / flag system')."""
+    (SURVEY.md section 5 'Config / flag system').
+
+    freeze_bn=True (or set_bn_frozen(True) later): fine-tuning mode.  In train() mode every BatchNorm normalises with its running
+    statistics as constants and leaves them untouched (layers.BatchNorm2d.frozen), so small batches -- B = 1 included, which the
+    ASPP's image-pool BatchNorm otherwise refuses -- do not overwrite the statistics of a loaded model; gamma / beta and every filter
+    still learn, dropout still applies.  (The reference's own freeze_bn method is shadowed by the attribute of the same name,
+    deeplab.py:32,41, and never runs.)  eval() mode is unchanged."""
 
     def __init__(self, activ_func=None, normalizer=None, backbone='resnet', output_stride=16, n_classes=9, in_channels=3,
                  freeze_bn=False, pretrained=False):
@@ -116,8 +123,24 @@ class DeepLab(nn.Module):
         self.decoder = Decoder(n_classes, low_c)
         self.in_channels = in_channels
         self.n_classes = n_classes
+        self.freeze_bn = False
+        if freeze_bn:
+            self.set_bn_frozen(True)
         if pretrained:
             self.load_pretrained_backbone()
+
+    def set_bn_frozen(self, on=True):
+        """Freeze (or release) every BatchNorm of the network and switch the statistics epilogue of the convs in front of them off (on).
+        Survives train() / eval() round trips; `self.freeze_bn` reports the state."""
+        from ..layers import DepthwiseConv3x3
+        on = bool(on)
+        for m in self.modules():
+            if isinstance(m, BatchNorm2d):
+                m.frozen = on
+            elif isinstance(m, (Conv2d, DepthwiseConv3x3)):
+                m.bn_frozen = on
+        self.freeze_bn = on
+        return self
 
     PRETRAINED_PATH = './data/models/resnet101-5d3b4d8f.pth'       # config.py:188 `defaults.pretrained`
 

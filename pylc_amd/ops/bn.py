@@ -339,6 +339,145 @@ class BnActFn(torch.autograd.Function):
         return (dy, dgamma, dbeta, None, None, g_out) + (None,) * 15
 
 
+class FrozenBnActFn(torch.autograd.Function):
+    """out = [dropout](act(y*scale + shift (+ residual))) with the coefficients of the RUNNING statistics, inside a training graph: the
+    BatchNorm of a fine-tuning step (DeepLab(freeze_bn=True)).  The statistics are constants, so nothing is reduced in the forward, no
+    running statistic is written, no collective is issued, one value per channel is legal, and the backward is ONE pass
+    (pylc_bn_frozen_bwd: dy = gamma invstd g, with [dgamma | dbeta] from the same walk) instead of the training mode's two.
+    All operands and results are fp32."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, running_mean, running_var, residual, relu, eps, want_amax, res_link, drop, into):
+        L.init()
+        ctx.set_materialize_grads(False)
+        ctx.res_link = res_link
+        y = as_nhwc(y)
+        b, c, h, w = y.shape
+        m = b * h * w
+        dev = y.device
+        st = stream()
+        yp = pitch_of(y)
+        coef = torch.empty(4 * c, device=dev)            # mean | invstd | scale | shift
+        mean, invstd, scale, shift = coef[:c], coef[c:2 * c], coef[2 * c:3 * c], coef[3 * c:]
+        # every call: gamma and beta move with each optimiser step
+        check(lib.pylc_bn_eval_coeffs_full(ptr(running_mean), ptr(running_var), ptr(gamma), ptr(beta), eps, c,
+                                           ptr(scale), ptr(shift), ptr(mean), ptr(invstd), st))
+        drop_p, drop_seed = drop if drop is not None else (0.0, 0)
+        res = as_nhwc(residual) if residual is not None else None
+        op_ = c
+        if into is not None:               # write into channels [c0, c0 + c) of a caller-owned concat buffer: into = ([buffer], c0)
+            buf, c0 = into[0][0], into[1]
+            op_ = pitch_of(buf)
+            if tuple(buf.shape[2:]) != (h, w) or buf.shape[0] != b or c0 % 4 or c0 + c > buf.shape[1]:
+                raise L.PylcError('bn_act into=: slice [%d, %d) does not fit the %s buffer' % (c0, c0 + c, tuple(buf.shape)))
+            out = buf[:, c0:c0 + c]
+        else:
+            out = empty_nhwc(b, c, h, w, dev)
+        amax = amax_slot(dev) if want_amax else None
+        needs_grad = any(ctx.needs_input_grad)
+        mask = None          # a ReLU behind a residual add: one bit per element for the backward (bn.hip "1-bit ReLU masks")
+        if relu and res is not None and c % 8 == 0 and drop_p == 0 and needs_grad and not _runtime.no_relu_bits:
+            mask = torch.empty(m * c // 8, dtype=torch.uint8, device=dev)
+        tm = _bn_time('frozen_apply%s%s%s' % ('+res' if res is not None else '', '+bits' if mask is not None else '', '+drop' if drop_p > 0 else ''),
+                      m, c, m * c * (8 + (4 if res is not None else 0) + (0.125 if mask is not None else 0)))
+        tm.__enter__()
+        if drop_p > 0 or mask is not None:
+            ex = _bn_extra(drop_p=drop_p, drop_seed=drop_seed)
+            if mask is not None:
+                ex.relu_mask = ptr(mask)
+            check(lib.pylc_bn_apply_ex(ptr(y), yp, ptr(scale), ptr(shift), ptr(res), pitch_of(res) if res is not None else 0,
+                                       ptr(out), op_, m, c, int(relu), ptr(amax), C.byref(ex), st))
+        else:
+            check(lib.pylc_bn_apply(ptr(y), yp, ptr(scale), ptr(shift), ptr(res), pitch_of(res) if res is not None else 0,
+                                    ptr(out), op_, m, c, int(relu), ptr(amax), st))
+        tm.__exit__()
+        # y is read again for the sums (a parameter takes a gradient) or for a ReLU mask recomputed from it; `out` only as the mask of
+        # a residual ReLU that left no bits
+        mask_out = relu and res is not None and mask is None
+        need_y = ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or (relu and res is None)
+        ctx.save_for_backward(y if (needs_grad and need_y) else None, out if (needs_grad and mask_out) else None, coef, mask)
+        ctx.cfg = (bool(relu), res is not None, (b, c, h, w))
+        ctx.g_param, ctx.b_param = gamma, beta
+        ctx.want_amax = want_amax
+        ctx.drop = (drop_p, drop_seed)
+        if want_amax:
+            ctx.mark_non_differentiable(amax)
+            return out, amax
+        return out
+
+    @staticmethod
+    def backward(ctx, dout, *_unused):
+        if dout is None:
+            return (None,) * 12
+        y, out, coef, mask = ctx.saved_tensors
+        relu, has_res, (b, c, h, w) = ctx.cfg
+        gamma, beta = ctx.g_param, ctx.b_param
+        dout = as_nhwc(dout)
+        m = b * h * w
+        dev = dout.device
+        st = stream()
+        mean, invstd = coef[:c], coef[c:2 * c]
+        scale, shift = (coef[2 * c:3 * c], coef[3 * c:]) if (relu and out is None and mask is None) else (None, None)
+        want_sums = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        # [dgamma | dbeta] go straight into the flat gradient arena when gamma/beta own adjacent slots there
+        tg, tb = _grad_target(gamma), _grad_target(beta)
+        direct = (tg is not None and tb is not None and tb.data_ptr() == tg.data_ptr() + 4 * c
+                  and ctx.needs_input_grad[1] and ctx.needs_input_grad[2])
+        sums = ws = None
+        if want_sums:
+            sums = torch.as_strided(tg, (2 * c,), (1,)) if direct else torch.empty(2 * c, device=dev)
+            ws = torch.empty(lib.pylc_bn_workspace_floats(m, c), device=dev)
+        drop_p, drop_seed = ctx.drop
+        lk = ctx.res_link
+        armed = lk is not None and lk.armed
+        want_res = has_res and ctx.needs_input_grad[5]
+        # without a ReLU (and without dropout) the residual's gradient IS dout: hand the tensor on (unless a conv is going to accumulate
+        # its dgrad into the buffer, which must then be ours)
+        res_is_dout = want_res and not relu and drop_p == 0 and not armed
+        g_out = empty_nhwc(b, c, h, w, dev) if (want_res and not res_is_dout) else None
+        dy = empty_nhwc(b, c, h, w, dev)
+        amax_dy = amax_slot(dev) if ctx.want_amax else None
+        ex = None
+        if drop_p > 0 or mask is not None:
+            ex = _bn_extra(drop_p=drop_p, drop_seed=drop_seed)
+            if mask is not None:
+                ex.relu_mask = ptr(mask)
+        msrc = 0.125 if mask is not None else (4 if out is not None else 0)
+        tm = _bn_time('frozen_bwd%s%s' % ('' if want_sums else '(no sums)', '+gres' if g_out is not None else ''), m, c,
+                      m * c * (8 + (4 if y is not None else 0) + msrc + (4 if g_out is not None else 0)))
+        tm.__enter__()
+        check(lib.pylc_bn_frozen_bwd(ptr(dout), pitch_of(dout), ptr(out), pitch_of(out) if out is not None else 0,
+                                     ptr(y), pitch_of(y) if y is not None else 0, ptr(mean), ptr(invstd), ptr(gamma), m, c, int(relu),
+                                     ptr(dy), c, ptr(g_out), c if g_out is not None else 0, ptr(amax_dy), ptr(scale), ptr(shift),
+                                     ptr(sums), ptr(ws), C.byref(ex) if ex is not None else None, st))
+        tm.__exit__()
+        if amax_dy is not None:
+            tag_amax(dy, amax_dy)       # the conv backward that receives dy reuses it
+        dgamma = dbeta = None
+        if direct:
+            _deliver_grad(gamma, tg)
+            _deliver_grad(beta, tb)
+        else:
+            if ctx.needs_input_grad[1]:
+                if tg is not None:
+                    tg.copy_(sums[:c])
+                    dgamma = _deliver_grad(gamma, tg)
+                else:
+                    dgamma = sums[:c].clone()
+            if ctx.needs_input_grad[2]:
+                if tb is not None:
+                    tb.copy_(sums[c:])
+                    dbeta = _deliver_grad(beta, tb)
+                else:
+                    dbeta = sums[c:].clone()
+        if res_is_dout:
+            g_out = dout
+        if g_out is not None and armed and lk.buf is None and lk.masked is None:
+            lk.buf = g_out           # the first conv's dgrad accumulates into it and returns it as x's whole gradient
+            g_out = None
+        return (dy if ctx.needs_input_grad[0] else None, dgamma, dbeta, None, None, g_out) + (None,) * 6
+
+
 def _drive_collectives(gens, group):
     """Run BatchNorm generators (BnActFn._forward / _backward) in lockstep: whatever they yield in one round is all-reduced as ONE message
     (a lone generator: its own tensor, no copy).  Returns their return values."""
@@ -420,7 +559,12 @@ class GroupBnActFn(torch.autograd.Function):
 
 def bn_act_group(specs, group):
     """bn_act for the BatchNorms of parallel branches, as one node (GroupBnActFn).  specs: one dict per layer with the keyword arguments of
-    bn_act (y, gamma, beta, running_mean, running_var + options); returns the outputs in order."""
+    bn_act (y, gamma, beta, running_mean, running_var + options); returns the outputs in order.  Frozen members (frozen=True) exchange
+    nothing: each is its own bn_act call."""
+    if any(sp.get('frozen') for sp in specs):
+        rest = [sp for sp in specs if not sp.get('frozen')]
+        outs = iter(bn_act_group(rest, group) if rest else [])
+        return [bn_act(**sp) if sp.get('frozen') else next(outs) for sp in specs]
     flat, marks = [], []
     for sp in specs:
         sp = dict(sp)
@@ -451,7 +595,23 @@ def bn_act_group(specs, group):
 
 
 def bn_act(y, gamma, beta, running_mean, running_var, residual=None, relu=True, training=True, eps=1e-5, momentum=0.1,
-           group=None, clamp_eps=False, res_link=None, out_planes=False, drop=None, into=None, sole=False, defer=False):
+           group=None, clamp_eps=False, res_link=None, out_planes=False, drop=None, into=None, sole=False, defer=False, frozen=False):
+    """frozen: the BatchNorm of a fine-tuning step (FrozenBnActFn) -- running statistics as constants inside a training graph, the fused
+    dropout still applied, no statistic written, no collective; fp32 in and out (out_planes / defer / sole, and a producer's wish for a
+    plane dy, are ignored)."""
+    if frozen:
+        if lib.pylc_get_conv_precision() == 3:
+            raise L.PylcError('frozen BatchNorm (freeze_bn) is not available in conv precision mode 3: its half activations are scaled with '
+                              'range bounds taken from batch statistics, which a frozen BatchNorm does not compute')
+        if drop is not None and not (_runtime.dropout_enabled and drop[0] > 0):
+            drop = None
+        ranged = ranges_needed()
+        res = FrozenBnActFn.apply(y, gamma, beta, running_mean, running_var, residual, relu, eps, ranged, res_link, drop, into)
+        if ranged:
+            out, tagv = res
+            tag_amax(out, tagv)
+            return out
+        return res
     pre = getattr(y, '_pylc_sums', None) if training else None
     dy_pl = bool(getattr(y, '_pylc_dy_pl', False)) and not _runtime.no_planes and _runtime.planes_dy
     out_planes = bool(out_planes) and ranges_needed() and not _runtime.no_planes
