@@ -611,6 +611,10 @@ int pylc_resize_area_u8(const unsigned char* src, int src_planar, int Cimg, int 
  * palette_rgb: device uint8 [n_classes][3], n_classes <= PYLC_MAX_CLASSES.  oh == H, ow == W is plain encoding. */
 int pylc_class_encode_resize(const unsigned char* rgb, int H, int W, const unsigned char* palette_rgb, int n_classes,
                              unsigned char* out, int oh, int ow, void* stream);
+/* The same with the value written for a colour that matches no palette entry as an argument (0..255, PYLC_ERR_ARG otherwise): 1 is
+ * pylc_class_encode_resize; an ignore label (255, say) keeps such pixels out of the loss, the scores and the profile. */
+int pylc_class_encode_resize_ex(const unsigned char* rgb, int H, int W, const unsigned char* palette_rgb, int n_classes,
+                                unsigned char* out, int oh, int ow, int unmatched_value, void* stream);
 /* pylc_image_pack_tiles on a float32 (is_u8 = 0) or uint8 (is_u8 = 1) image [Cimg][H][W]: same arguments and arithmetic,
  * bit-identical tiles for equal pixel values (csrc/stitch.hip). */
 int pylc_image_pack_tiles_ex(const void* img, int is_u8, int Cimg, int H, int W, int tile, int stride, int first_tile,
@@ -659,6 +663,10 @@ int pylc_augment_tiles(const unsigned char* img_tiles, const unsigned char* mask
  * zeroed by the caller; integer atomics make the result exact and order-independent. */
 int pylc_confusion_matrix(const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C,
                           int force_coverage, unsigned long long* cm, void* stream);
+/* With an ignore label: a pixel whose true label (after force_coverage) equals ignore_index, compared after widening, or lies outside
+ * 0..C-1 is left out of cm; n_skipped (NULL, or [2]) has the number of out-of-range ones ADDED to [0] and of ignored ones to [1]. */
+int pylc_confusion_matrix_ex(const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C,
+                             int force_coverage, unsigned long long* cm, int ignore_index, unsigned long long* n_skipped, void* stream);
 /* The same counts straight from a network's logits, with the argmax fused in (csrc/score.hip): logits are N pixel
  * rows of `pitch` floats (pitch >= C, C in 2..PYLC_MAX_CLASSES; the NHWC tensor a net returns), read with 16-byte loads when pitch % 4 == 0
  * and the base is 16-byte aligned, else float by float.  The class of a pixel is its FIRST maximum (strict `>` scan, numpy's argmax; NaN
@@ -670,6 +678,10 @@ int pylc_confusion_matrix(const void* y_true, int true_bytes, const void* y_pred
  * out of range, N <= 0 or N > 2^39 (the bound of a block's 32-bit counters): PYLC_ERR_ARG, nothing is launched. */
 int pylc_logits_score(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
                       unsigned long long* counts, void* stream);
+/* With an ignore label: counts is [C*C + 2]; a pixel whose target equals ignore_index (compared after widening; an index inside 0..C-1
+ * is allowed) adds to counts[C*C + 1], any other target outside 0..C-1 to counts[C*C], and neither enters the matrix. */
+int pylc_logits_score_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
+                         int ignore_index, unsigned long long* counts, void* stream);
 
 /* The general form: ((x - mean[c]) / std[c]) / denom on float (is_u8 = 0) or uint8 (is_u8 = 1) tiles.  denom = 255 is
  * pylc_image_pack[_u8]; denom = 1 is the reference's grayscale `default=True` branch, which omits the division by 255
@@ -707,6 +719,20 @@ int pylc_multiloss_bwd(const float* logits, int pitch, const int64_t* target, lo
                        const float* class_weights, const float* stats, double n_global,
                        float w_ce, float w_dice, float w_focal, const float* grad_scale,
                        float* dlogits, int dpitch, unsigned int* amax_bits, void* stream);
+/* The loss head with an ignore label.  target: uint8 (target_bytes 1, any byte address) or int64 (8) [N].  A pixel
+ * is IGNORED when its target, widened, equals ignore_index (an index inside 0..C-1 is allowed), VALID when it is not ignored and lies in
+ * 0..C-1, BAD otherwise.  Only valid pixels enter the sums (same stats layout); ignored and bad pixels are not loaded, never index anything,
+ * and receive +0.0 in every stored channel of dlogits.  n_bad (may be NULL): the number of bad pixels is ADDED into it.  The pixel count of
+ * the mean terms is the number of valid pixels, read from the (all-reduced) stats as the sum of the class counts in double -- exact up to
+ * 2^24 valid pixels per class; with none, all four losses, all of dlogits and the amax bits are 0.  With nothing ignored or bad the results
+ * are bit-identical to the entry points above.  A target_bytes other than 1 / 8, a NULL target, pitch < C, N <= 0, C outside
+ * 2..PYLC_MAX_CLASSES: PYLC_ERR_ARG, nothing is launched. */
+int pylc_multiloss_stats_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                            const float* class_weights, float* stats, float* workspace, unsigned long long* n_bad, void* stream);
+int pylc_multiloss_finalize_ex(const float* stats, int C, float w_ce, float w_dice, float w_focal, float* losses, void* stream);
+int pylc_multiloss_bwd_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                          const float* class_weights, const float* stats, float w_ce, float w_dice, float w_focal,
+                          const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimiser: torch.nn.utils.clip_grad_norm_(params, 0.5) models/model.py:326 + torch.optim.AdamW

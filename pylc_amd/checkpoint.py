@@ -159,6 +159,6 @@ def load_into(model, path, resume=False):
         if os.path.exists(spath):             # a run that scored its validation passes (trainer(score=True)) goes on scoring them
             if getattr(model, 'scores', None) is None:
                 from .metrics import ScoreLog
-                model.scores = ScoreLog(model.meta.n_classes)
+                model.scores = ScoreLog(model.meta.n_classes, getattr(model.meta, 'ignore_index', None))
             model.scores.load(spath)
     return data

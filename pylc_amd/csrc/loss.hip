@@ -4,6 +4,17 @@
 // Replaces models/modules/loss.py: ce_loss :66-69, dice_loss :137-146, focal_loss :174-189, forward :107-112
 // (the reference runs 3 softmaxes + 2 one-hots + ~20 elementwise passes over B*C*H*W).
 // logits are NHWC [N pixels][pitch]; one thread owns one pixel (its C logits are contiguous).
+//
+// Ignore label (pylc_multiloss_*_ex): the kernels are templates over the target's width (TT: int64 or uint8, read at
+// any byte address) and IGN.  With IGN a pixel is VALID when its target, widened to 64 bits, is not `ignore` and lies in 0..C-1; every
+// other pixel is skipped before its logits row is loaded (unpainted regions are blobs: whole waves skip), contributes to no sum, is never
+// used as an index, and gets an all-zero gradient row.  A valid pixel runs the very same per-pixel code as without IGN, in the same
+// thread of the same grid, so <int64, IGN = false> (the entry points without _ex) is the code as it was, and the _ex path with nothing
+// skipped gives the same bits.  The number of valid pixels is not passed in: it is the sum of the class counts stats[3 + 2C + c], taken in
+// double from the (all-reduced) statistics.  Those counts are exact as long as a class holds at most 2^24 = 16 777 216 valid pixels
+// globally: a thread's and a block's partial counts are sums of ones in fp32 (exact below 2^24 per block, i.e. for N < 2^34),
+// column_sum_kernel adds the <= 1024 block partials in fp64 (exact), and only the final store of a class total to the fp32 stats (and a
+// data-parallel all-reduce of it) rounds -- to nearest, relative error <= 2^-25 per class beyond 2^24 pixels in it.
 #include "common.h"
 
 namespace pylc {
@@ -29,20 +40,28 @@ __device__ __forceinline__ void softmax_px(const float* __restrict__ z, float (&
 }
 
 // partial[block][3 + 3C]
-template <int C>
-__global__ __launch_bounds__(256) void multiloss_stats_kernel(const float* __restrict__ logits, int pitch, const long long* __restrict__ target,
-                                                              long long N, const float* __restrict__ cw, float* __restrict__ partial) {
+// n_bad (IGN only, may be NULL): the number of skipped pixels that are not `ignore` is ADDED into it
+template <int C, typename TT, bool IGN>
+__global__ __launch_bounds__(256) void multiloss_stats_kernel(const float* __restrict__ logits, int pitch, const TT* __restrict__ target,
+                                                              long long N, const float* __restrict__ cw, float* __restrict__ partial,
+                                                              long long ignore, unsigned long long* __restrict__ n_bad) {
     __shared__ float red[4];
     float acc[3 + 3 * C];
 #pragma unroll
     for (int k = 0; k < 3 + 3 * C; ++k) acc[k] = 0.f;
+    unsigned int bad = 0;
     for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long long)gridDim.x * blockDim.x) {
+        const long long tl = (long long)target[n];
+        if constexpr (IGN) {
+            if (tl == ignore) continue;
+            if ((unsigned long long)tl >= (unsigned long long)C) { ++bad; continue; }
+        }
         float z[C], p[C], lse;
         const float* src = logits + n * pitch;
 #pragma unroll
         for (int c = 0; c < C; ++c) z[c] = src[c];
         softmax_px<C>(z, p, lse);
-        const int t = (int)target[n];
+        const int t = (int)tl;
         float zt = 0.f, pt = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
@@ -66,13 +85,36 @@ __global__ __launch_bounds__(256) void multiloss_stats_kernel(const float* __res
         const float s = block_sum_256(acc[k], red);
         if (threadIdx.x == 0) dst[k] = s;
     }
+    if constexpr (IGN) {
+        if (n_bad != nullptr) {
+            unsigned long long wave_bad = 0;
+            for (int l = 0; l < 64; ++l) wave_bad += (unsigned)__shfl((int)bad, l, 64);
+            if ((threadIdx.x & 63) == 0 && wave_bad != 0) atomicAdd(n_bad, wave_bad);
+        }
+    }
 }
 
+// the number of valid pixels of (all-reduced) stats: the sum of the class counts, in double
+__device__ __forceinline__ double stats_n_valid(const float* __restrict__ stats, int C) {
+    double n = 0.0;
+    for (int c = 0; c < C; ++c) n += (double)stats[3 + 2 * C + c];
+    return n;
+}
+
+// FROM_STATS: n is the valid count of the stats (the argument is not used); a zero count or weight sum gives 0, never a division by zero
+template <bool FROM_STATS>
 __global__ void multiloss_finalize_kernel(const float* __restrict__ stats, double n, int C, float w_ce, float w_d, float w_f,
                                           float* __restrict__ losses) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const double ce = (double)stats[0] / (double)stats[1];
-    const double fl = (double)stats[2] / n;
+    double ce, fl;
+    if constexpr (FROM_STATS) {
+        n = stats_n_valid(stats, C);
+        ce = stats[1] > 0.f ? (double)stats[0] / (double)stats[1] : 0.0;
+        fl = n > 0.0 ? (double)stats[2] / n : 0.0;
+    } else {
+        ce = (double)stats[0] / (double)stats[1];
+        fl = (double)stats[2] / n;
+    }
     double dsc = 0.0;
     for (int c = 0; c < C; ++c) {
         const double I = stats[3 + c], K = (double)stats[3 + C + c] + (double)stats[3 + 2 * C + c];
@@ -85,12 +127,16 @@ __global__ void multiloss_finalize_kernel(const float* __restrict__ stats, doubl
     losses[3] = (float)fl;
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void multiloss_bwd_kernel(const float* __restrict__ logits, int pitch, const long long* __restrict__ target,
+typedef float loss_f4 __attribute__((ext_vector_type(4)));
+
+// IGN: inv_n is not used (1 / the valid count of `stats` instead, rounded as the host rounds 1 / n_global for the plain form); skipped
+// pixels write a zero row of Cstore floats -- with 16-byte stores when zero16 (dpitch % 4 == 0 and an aligned base, so Cstore % 4 == 0)
+template <int C, typename TT, bool IGN>
+__global__ __launch_bounds__(256) void multiloss_bwd_kernel(const float* __restrict__ logits, int pitch, const TT* __restrict__ target,
                                                             long long N, const float* __restrict__ cw, const float* __restrict__ stats,
                                                             float inv_n, float w_ce, float w_d, float w_f,
                                                             const float* __restrict__ grad_scale, float* __restrict__ dlogits, int dpitch,
-                                                            int Cstore, unsigned* __restrict__ amax_out) {
+                                                            int Cstore, unsigned* __restrict__ amax_out, long long ignore, int zero16) {
     // per-class Dice coefficients: dL_d/dp_c(n) = -[2 o_c (K_c + s) - (2 I_c + s)] / (K_c + s)^2 / C = o_c * A_c + B_c
     float dA[C], dB[C];
 #pragma unroll
@@ -101,15 +147,34 @@ __global__ __launch_bounds__(256) void multiloss_bwd_kernel(const float* __restr
         dB[c] = (2.f * I + kDiceSmooth) / (den * den) / (float)C;
     }
     const float gs = grad_scale != nullptr ? grad_scale[0] : 1.f;
-    const float ce_norm = w_ce / stats[1];     // unweighted: stats[1] = N
+    float ce_norm;
+    if constexpr (IGN) {
+        const double nv = stats_n_valid(stats, C);
+        inv_n = nv > 0.0 ? (float)(1.0 / nv) : 0.f;
+        ce_norm = stats[1] > 0.f ? w_ce / stats[1] : 0.f;
+    } else {
+        ce_norm = w_ce / stats[1];             // unweighted: stats[1] = N
+    }
     float gmax = 0.f;                          // max |dlogits|: the range the conv backward that receives them scales its operand with
     for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long long)gridDim.x * blockDim.x) {
+        const long long tl = (long long)target[n];
+        if constexpr (IGN) {
+            if (tl == ignore || (unsigned long long)tl >= (unsigned long long)C) {
+                float* zrow = dlogits + n * dpitch;
+                if (zero16) {
+                    for (int c = 0; c < Cstore; c += 4) *reinterpret_cast<loss_f4*>(zrow + c) = loss_f4{0.f, 0.f, 0.f, 0.f};
+                } else {
+                    for (int c = 0; c < Cstore; ++c) zrow[c] = 0.f;
+                }
+                continue;
+            }
+        }
         float z[C], p[C], lse;
         const float* src = logits + n * pitch;
 #pragma unroll
         for (int c = 0; c < C; ++c) z[c] = src[c];
         softmax_px<C>(z, p, lse);
-        const int t = (int)target[n];
+        const int t = (int)tl;
         float pt = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) pt = (c == t) ? p[c] : pt;
@@ -154,16 +219,27 @@ extern "C" size_t pylc_multiloss_workspace_floats(long long N, int C) {
     return (size_t)kLossBlocks * (3 + 3 * (size_t)C);
 }
 
-extern "C" int pylc_multiloss_stats(const float* logits, int pitch, const int64_t* target, long long N, int C, const float* cw, float* stats,
-                                    float* workspace, void* stream) {
-    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats: n_classes=%d unsupported (2..%d)", C, MAXC);
-    PYLC_REQUIRE(logits && target && stats && workspace && N > 0 && pitch >= C, "multiloss_stats: bad arguments");
+static int multiloss_stats_impl(const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N, int C, long long ignore,
+                                const float* cw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
     hipStream_t st = as_stream(stream);
     const int blocks = (int)(cdiv<long long>(N, 256) < kLossBlocks ? cdiv<long long>(N, 256) : kLossBlocks);
-    const long long* tgt = reinterpret_cast<const long long*>(target);
-#define LAUNCH_STATS(CC) hipLaunchKernelGGL((multiloss_stats_kernel<CC>), dim3(blocks), dim3(256), 0, st, logits, pitch, tgt, N, cw, workspace)
-    PYLC_FOR_C(LAUNCH_STATS)
+#define LAUNCH_STATS_T(CC, TT, IGN)                                                                                                          \
+    hipLaunchKernelGGL((multiloss_stats_kernel<CC, TT, IGN>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
+                       workspace, ignore, n_bad)
+    if (!ign) {
+#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, false)
+        PYLC_FOR_C(LAUNCH_STATS)
 #undef LAUNCH_STATS
+    } else if (target_bytes == 8) {
+#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, true)
+        PYLC_FOR_C(LAUNCH_STATS)
+#undef LAUNCH_STATS
+    } else {
+#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, unsigned char, true)
+        PYLC_FOR_C(LAUNCH_STATS)
+#undef LAUNCH_STATS
+    }
+#undef LAUNCH_STATS_T
     PYLC_LAUNCH_CHECK();
     const int K = 3 + 3 * C;
     hipLaunchKernelGGL(column_sum_kernel, dim3(cdiv(K, 8)), dim3(256), 0, st, workspace, blocks, K, stats);
@@ -171,10 +247,68 @@ extern "C" int pylc_multiloss_stats(const float* logits, int pitch, const int64_
     return PYLC_OK;
 }
 
+extern "C" int pylc_multiloss_stats(const float* logits, int pitch, const int64_t* target, long long N, int C, const float* cw, float* stats,
+                                    float* workspace, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats: n_classes=%d unsupported (2..%d)", C, MAXC);
+    PYLC_REQUIRE(logits && target && stats && workspace && N > 0 && pitch >= C, "multiloss_stats: bad arguments");
+    return multiloss_stats_impl(logits, pitch, target, 8, false, N, C, 0, cw, stats, workspace, nullptr, stream);
+}
+
+extern "C" int pylc_multiloss_stats_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                                       const float* cw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats_ex: n_classes=%d unsupported (2..%d)", C, MAXC);
+    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_stats_ex: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
+    PYLC_REQUIRE(target, "multiloss_stats_ex: target is NULL");
+    PYLC_REQUIRE(pitch >= C, "multiloss_stats_ex: pitch=%d below n_classes=%d", pitch, C);
+    PYLC_REQUIRE(N > 0, "multiloss_stats_ex: N=%lld is not positive", N);
+    PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_ex: logits, stats or workspace is NULL");
+    PYLC_REQUIRE((target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0) && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0,
+                 "multiloss_stats_ex: a buffer is not aligned to its element");
+    return multiloss_stats_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, stats, workspace, n_bad, stream);
+}
+
 extern "C" int pylc_multiloss_finalize(const float* stats, double n_global, int C, float w_ce, float w_dice, float w_focal, float* losses,
                                        void* stream) {
     PYLC_REQUIRE(stats && losses && n_global > 0 && C >= 2 && C <= MAXC, "multiloss_finalize: bad arguments");
-    hipLaunchKernelGGL(multiloss_finalize_kernel, dim3(1), dim3(64), 0, as_stream(stream), stats, n_global, C, w_ce, w_dice, w_focal, losses);
+    hipLaunchKernelGGL(multiloss_finalize_kernel<false>, dim3(1), dim3(64), 0, as_stream(stream), stats, n_global, C, w_ce, w_dice, w_focal, losses);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_multiloss_finalize_ex(const float* stats, int C, float w_ce, float w_dice, float w_focal, float* losses, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_finalize_ex: n_classes=%d unsupported (2..%d)", C, MAXC);
+    PYLC_REQUIRE(stats && losses, "multiloss_finalize_ex: stats or losses is NULL");
+    hipLaunchKernelGGL(multiloss_finalize_kernel<true>, dim3(1), dim3(64), 0, as_stream(stream), stats, 0.0, C, w_ce, w_dice, w_focal, losses);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+static int multiloss_bwd_impl(const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N, int C, long long ignore,
+                              const float* cw, const float* stats, double n_global, float w_ce, float w_dice, float w_focal,
+                              const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    hipStream_t st = as_stream(stream);
+    if (amax_bits != nullptr) PYLC_HIP(hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st));
+    const int blocks = (int)(cdiv<long long>(N, 256) < 4096 ? cdiv<long long>(N, 256) : 4096);
+    const int Cstore = ((C + 3) & ~3) <= dpitch ? ((C + 3) & ~3) : C;
+    const float inv_n = ign ? 0.f : (float)(1.0 / n_global);
+    const int zero16 = dpitch % 4 == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;      // then Cstore = roundup4(C) <= dpitch
+#define LAUNCH_BWD_T(CC, TT, IGN)                                                                                                              \
+    hipLaunchKernelGGL((multiloss_bwd_kernel<CC, TT, IGN>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
+                       stats, inv_n, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, Cstore, amax_bits, ignore, zero16)
+    if (!ign) {
+#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, false)
+        PYLC_FOR_C(LAUNCH_BWD)
+#undef LAUNCH_BWD
+    } else if (target_bytes == 8) {
+#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, true)
+        PYLC_FOR_C(LAUNCH_BWD)
+#undef LAUNCH_BWD
+    } else {
+#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, unsigned char, true)
+        PYLC_FOR_C(LAUNCH_BWD)
+#undef LAUNCH_BWD
+    }
+#undef LAUNCH_BWD_T
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
 }
@@ -184,17 +318,20 @@ extern "C" int pylc_multiloss_bwd(const float* logits, int pitch, const int64_t*
                                   float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
     PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd: n_classes=%d unsupported (2..%d)", C, MAXC);      // before amax_bits is cleared
     PYLC_REQUIRE(logits && target && stats && dlogits && N > 0 && pitch >= C && dpitch >= C && n_global > 0, "multiloss_bwd: bad arguments");
-    hipStream_t st = as_stream(stream);
-    if (amax_bits != nullptr) PYLC_HIP(hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st));
-    const int blocks = (int)(cdiv<long long>(N, 256) < 4096 ? cdiv<long long>(N, 256) : 4096);
-    const long long* tgt = reinterpret_cast<const long long*>(target);
-    const int Cstore = ((C + 3) & ~3) <= dpitch ? ((C + 3) & ~3) : C;
-    const float inv_n = (float)(1.0 / n_global);
-#define LAUNCH_BWD(CC)                                                                                                                    \
-    hipLaunchKernelGGL((multiloss_bwd_kernel<CC>), dim3(blocks), dim3(256), 0, st, logits, pitch, tgt, N, cw, stats, inv_n, w_ce, w_dice, \
-                       w_focal, grad_scale, dlogits, dpitch, Cstore, amax_bits)
-    PYLC_FOR_C(LAUNCH_BWD)
-#undef LAUNCH_BWD
-    PYLC_LAUNCH_CHECK();
-    return PYLC_OK;
+    return multiloss_bwd_impl(logits, pitch, target, 8, false, N, C, 0, cw, stats, n_global, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch,
+                              amax_bits, stream);
+}
+
+extern "C" int pylc_multiloss_bwd_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                                     const float* cw, const float* stats, float w_ce, float w_dice, float w_focal, const float* grad_scale,
+                                     float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd_ex: n_classes=%d unsupported (2..%d)", C, MAXC);   // before amax_bits is cleared
+    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_bwd_ex: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
+    PYLC_REQUIRE(target, "multiloss_bwd_ex: target is NULL");
+    PYLC_REQUIRE(pitch >= C && dpitch >= C, "multiloss_bwd_ex: pitch=%d or dpitch=%d below n_classes=%d", pitch, dpitch, C);
+    PYLC_REQUIRE(N > 0, "multiloss_bwd_ex: N=%lld is not positive", N);
+    PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_ex: logits, stats or dlogits is NULL");
+    PYLC_REQUIRE(target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0, "multiloss_bwd_ex: an int64 target is not 8-byte aligned");
+    return multiloss_bwd_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, stats, 1.0, w_ce, w_dice, w_focal,
+                              grad_scale, dlogits, dpitch, amax_bits, stream);
 }

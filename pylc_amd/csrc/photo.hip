@@ -146,11 +146,11 @@ __global__ __launch_bounds__(256) void resize_area_kernel(const unsigned char* _
 }
 
 // out[oy][ox] = class_encode(rgb[min(floor(oy*fy), H-1)][min(floor(ox*fx), W-1)]): the LAST palette index whose colour matches (the
-// reference's loop overwrites), 1 when none does (its np.ones).  Four consecutive flat pixels per lane, their twelve loads issued together,
+// reference's loop overwrites), `unmatched` when none does (1 is its np.ones).  Four consecutive flat pixels per lane, their twelve loads issued together,
 // one dword store.  (Flat sizes < 2^31: checked.)
 __global__ __launch_bounds__(256) void class_encode_resize_kernel(const unsigned char* __restrict__ rgb, int H, int W,
                                                                   const unsigned char* __restrict__ palette, int C, unsigned char* __restrict__ out,
-                                                                  int oh, int ow, double fy, double fx) {
+                                                                  int oh, int ow, double fy, double fx, unsigned int unmatched) {
     __shared__ unsigned int pal[PYLC_MAX_CLASSES];
     if (threadIdx.x < C) pal[threadIdx.x] = palette[3 * threadIdx.x] | (palette[3 * threadIdx.x + 1] << 8) | (palette[3 * threadIdx.x + 2] << 16);
     __syncthreads();
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void class_encode_resize_kernel(const unsigned
         unsigned int packed = 0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            unsigned int cls = 1;
+            unsigned int cls = unmatched;
             for (int k = 0; k < C; ++k)
                 if (pal[k] == colour[p]) cls = k;
             packed |= cls << (8 * p);
@@ -225,14 +225,20 @@ extern "C" int pylc_resize_area_u8(const unsigned char* src, int src_planar, int
     return PYLC_OK;
 }
 
-extern "C" int pylc_class_encode_resize(const unsigned char* rgb, int H, int W, const unsigned char* palette_rgb, int n_classes,
-                                        unsigned char* out, int oh, int ow, void* stream) {
+extern "C" int pylc_class_encode_resize_ex(const unsigned char* rgb, int H, int W, const unsigned char* palette_rgb, int n_classes,
+                                           unsigned char* out, int oh, int ow, int unmatched_value, void* stream) {
     PYLC_REQUIRE(rgb && palette_rgb && out && H > 0 && W > 0 && oh > 0 && ow > 0, "class_encode_resize: bad arguments");
     PYLC_REQUIRE(n_classes >= 1 && n_classes <= PYLC_MAX_CLASSES, "class_encode_resize: n_classes=%d outside 1..%d", n_classes, PYLC_MAX_CLASSES);
+    PYLC_REQUIRE(unmatched_value >= 0 && unmatched_value <= 255, "class_encode_resize: unmatched_value=%d outside 0..255", unmatched_value);
     PYLC_REQUIRE((long long)H * W * 3 < (1LL << 31) && (long long)oh * ow < (1LL << 31), "class_encode_resize: image too large");
     const long long groups = cdiv<long long>((long long)oh * ow, 4);
     hipLaunchKernelGGL(class_encode_resize_kernel, dim3(ph_grid(groups)), dim3(256), 0, as_stream(stream), rgb, H, W, palette_rgb, n_classes, out,
-                       oh, ow, 1.0 / ((double)oh / H), 1.0 / ((double)ow / W));
+                       oh, ow, 1.0 / ((double)oh / H), 1.0 / ((double)ow / W), (unsigned int)unmatched_value);
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
+}
+
+extern "C" int pylc_class_encode_resize(const unsigned char* rgb, int H, int W, const unsigned char* palette_rgb, int n_classes,
+                                        unsigned char* out, int oh, int ow, void* stream) {
+    return pylc_class_encode_resize_ex(rgb, H, W, palette_rgb, n_classes, out, oh, ow, 1, stream);      // the reference's np.ones
 }

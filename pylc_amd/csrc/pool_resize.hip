@@ -25,7 +25,7 @@ struct PoolPlanes { _Float16* planes; long long plane_stride; const unsigned* bo
 __device__ __forceinline__ float pool_pow2_scale(unsigned bits) {      // conv_common.h pow2_scale_for: bound -> [2^14, 2^15)
     int e = (int)((bits >> 23) & 0xFFu);
     int se = 127 + 14 - (e - 127);
-    se = se < 1 ? 1 : (se > 254 ? 254 : se);
+    se = se < 1 ? 1 : (se > 242 ? 242 : se);
     return __uint_as_float((unsigned)se << 23);
 }
 
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void gap_fwd_planes_kernel(const _Float16* __r
     const int cv = blockIdx.x * 16 + tx;
     int e = (int)((*amax >> 23) & 0xFFu);                      // 1 / (the power-of-two scale of the tensor's range bound): conv_common.h pow2_scale_for
     int se = 127 + 14 - (e - 127);
-    se = se < 1 ? 1 : (se > 254 ? 254 : se);
+    se = se < 1 ? 1 : (se > 242 ? 242 : se);
     const float inv = 1.f / __uint_as_float((unsigned)se << 23);
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
     if (cv < CV) {

@@ -16,6 +16,10 @@
 // broadcast, a ballot per pixel slot finds every pixel of the wave with that cell, the leader adds the population count, those pixels
 // retire.  SCORE_ROUNDS such rounds clear a blob mask; what is left after them (uniformly random cells: ~80 distinct ones) goes to LDS with
 // one atomic per pixel, where it hardly collides.  Either way every pixel is added exactly once.
+//
+// pylc_logits_score_ex is the same kernel with one more cell: a target equal to the ignore label is counted in cell
+// C*C + 1 instead of the matrix or the out-of-range cell C*C.  The label is a kernel argument; without it the extra cell stays empty and is
+// not written back.
 #include "common.h"
 
 namespace pylc {
@@ -68,9 +72,10 @@ __device__ __forceinline__ void score_load(ScorePixels<C, TT>& px, const float* 
     }
 }
 
+// has_ign: a target equal to `ign` (compared after widening) goes to cell C*C + 1 instead of the matrix or the bad cell C*C
 template <int C, typename TT, bool HAS_T>
 __device__ __forceinline__ void score_work(const ScorePixels<C, TT>& px, long long N, long long first, unsigned char* __restrict__ mask,
-                                           unsigned int* hist) {
+                                           unsigned int* hist, bool has_ign, long long ign) {
     int cls[4], cell[4];
     bool ok[4];
 #pragma unroll
@@ -94,7 +99,8 @@ __device__ __forceinline__ void score_work(const ScorePixels<C, TT>& px, long lo
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const unsigned long long t = (unsigned long long)(long long)px.t[k];        // a negative int64 target is out of range too
-        cell[k] = !ok[k] ? -1 : (t < (unsigned long long)C ? (int)t * C + cls[k] : C * C);
+        const bool ignored = has_ign && (long long)px.t[k] == ign;
+        cell[k] = !ok[k] ? -1 : ignored ? C * C + 1 : (t < (unsigned long long)C ? (int)t * C + cls[k] : C * C);
     }
     // wave-level rounds: every lane of the wave is here (the caller's loop is wave-uniform), retired pixels hold -1
     const int lane = threadIdx.x & 63;
@@ -121,10 +127,11 @@ __device__ __forceinline__ void score_work(const ScorePixels<C, TT>& px, long lo
 // HAS_T: a target and counts are given (else mask only: TT is not used)
 template <int C, typename TT, bool VEC, bool HAS_T>
 __global__ __launch_bounds__(256) void logits_score_kernel(const float* __restrict__ logits, int pitch, const TT* __restrict__ target, long long N,
-                                                            int off, unsigned char* __restrict__ mask, unsigned long long* __restrict__ counts) {
-    __shared__ unsigned int hist[C * C + 1];
+                                                            int off, unsigned char* __restrict__ mask, unsigned long long* __restrict__ counts,
+                                                            int has_ign, long long ign) {
+    __shared__ unsigned int hist[C * C + 2];
     if constexpr (HAS_T) {
-        for (int i = threadIdx.x; i < C * C + 1; i += 256) hist[i] = 0;
+        for (int i = threadIdx.x; i < C * C + 2; i += 256) hist[i] = 0;
         __syncthreads();
     }
     const long long groups = (N + off + 3) >> 2;
@@ -138,29 +145,29 @@ __global__ __launch_bounds__(256) void logits_score_kernel(const float* __restri
     score_load<C, TT, VEC, HAS_T>(a, logits, pitch, target, N, 4 * g - off);
     while (g - lane < groups) {
         score_load<C, TT, VEC, HAS_T>(b, logits, pitch, target, N, 4 * (g + step) - off);
-        score_work<C, TT, HAS_T>(a, N, 4 * g - off, mask, hist);
+        score_work<C, TT, HAS_T>(a, N, 4 * g - off, mask, hist, has_ign != 0, ign);
         g += step;
         if (g - lane >= groups) break;
         score_load<C, TT, VEC, HAS_T>(a, logits, pitch, target, N, 4 * (g + step) - off);
-        score_work<C, TT, HAS_T>(b, N, 4 * g - off, mask, hist);
+        score_work<C, TT, HAS_T>(b, N, 4 * g - off, mask, hist, has_ign != 0, ign);
         g += step;
     }
     if constexpr (HAS_T) {
         __syncthreads();
-        for (int i = threadIdx.x; i < C * C + 1; i += 256)
+        for (int i = threadIdx.x; i < C * C + 1 + has_ign; i += 256)      // (cell C*C + 1 exists in `counts` only with has_ign, and is only then used)
             if (hist[i]) atomicAdd(&counts[i], (unsigned long long)hist[i]);
     }
 }
 
 template <int C, typename TT, bool HAS_T>
 static void score_launch(bool vec, int blocks, hipStream_t st, const float* logits, int pitch, const void* target, long long N, int off,
-                         unsigned char* mask, unsigned long long* counts) {
+                         unsigned char* mask, unsigned long long* counts, int has_ign, long long ign) {
     if (vec)
         hipLaunchKernelGGL((logits_score_kernel<C, TT, true, HAS_T>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target),
-                           N, off, mask, counts);
+                           N, off, mask, counts, has_ign, ign);
     else
         hipLaunchKernelGGL((logits_score_kernel<C, TT, false, HAS_T>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target),
-                           N, off, mask, counts);
+                           N, off, mask, counts, has_ign, ign);
 }
 
 #define PYLC_SCORE_FOR_C(MACRO)                                                                                        \
@@ -176,8 +183,8 @@ static void score_launch(bool vec, int blocks, hipStream_t st, const float* logi
 
 using namespace pylc;
 
-extern "C" int pylc_logits_score(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
-                                 unsigned long long* counts, void* stream) {
+static int logits_score_impl(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
+                             unsigned long long* counts, int has_ign, long long ign, void* stream) {
     PYLC_REQUIRE(logits, "logits_score: logits is NULL");
     PYLC_REQUIRE(mask || counts, "logits_score: mask and counts are both NULL, nothing to compute");
     PYLC_REQUIRE(C >= 2 && C <= SCORE_MAXC, "logits_score: n_classes=%d unsupported (2..%d)", C, SCORE_MAXC);
@@ -196,18 +203,28 @@ extern "C" int pylc_logits_score(const float* logits, int pitch, const void* tar
     const int blocks = (int)(want < SCORE_GRID ? want : SCORE_GRID);
     hipStream_t st = as_stream(stream);
     if (!counts) {                                                                 // mask only: a target, if any, is not read
-#define LAUNCH_SC(CC) score_launch<CC, unsigned char, false>(vec, blocks, st, logits, pitch, nullptr, N, off, mask, nullptr)
+#define LAUNCH_SC(CC) score_launch<CC, unsigned char, false>(vec, blocks, st, logits, pitch, nullptr, N, off, mask, nullptr, 0, 0)
         PYLC_SCORE_FOR_C(LAUNCH_SC)
 #undef LAUNCH_SC
     } else if (target_bytes == 8) {
-#define LAUNCH_SC(CC) score_launch<CC, long long, true>(vec, blocks, st, logits, pitch, target, N, off, mask, counts)
+#define LAUNCH_SC(CC) score_launch<CC, long long, true>(vec, blocks, st, logits, pitch, target, N, off, mask, counts, has_ign, ign)
         PYLC_SCORE_FOR_C(LAUNCH_SC)
 #undef LAUNCH_SC
     } else {
-#define LAUNCH_SC(CC) score_launch<CC, unsigned char, true>(vec, blocks, st, logits, pitch, target, N, off, mask, counts)
+#define LAUNCH_SC(CC) score_launch<CC, unsigned char, true>(vec, blocks, st, logits, pitch, target, N, off, mask, counts, has_ign, ign)
         PYLC_SCORE_FOR_C(LAUNCH_SC)
 #undef LAUNCH_SC
     }
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
+}
+
+extern "C" int pylc_logits_score(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
+                                 unsigned long long* counts, void* stream) {
+    return logits_score_impl(logits, pitch, target, target_bytes, N, C, mask, counts, 0, 0, stream);
+}
+
+extern "C" int pylc_logits_score_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
+                                    int ignore_index, unsigned long long* counts, void* stream) {
+    return logits_score_impl(logits, pitch, target, target_bytes, N, C, mask, counts, 1, (long long)ignore_index, stream);
 }

@@ -200,20 +200,53 @@ extern "C" int pylc_image_pack_tiles_ex(const void* img, int is_u8, int Cimg, in
 // on the fly when force_coverage != 0.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace pylc {
-template <typename TT, typename TP>
+// IGN: pixels whose true label equals `ignore` (compared after widening) or lies outside 0..C-1 are left out of the matrix and counted in
+// skipped[1] / skipped[0].  Without IGN a pixel with either label out of range is dropped silently, as before.
+template <typename TT, typename TP, bool IGN>
 __global__ __launch_bounds__(256) void confusion_kernel(const TT* __restrict__ yt, const TP* __restrict__ yp, long long n, int C,
-                                                         int force_coverage, unsigned long long* __restrict__ cm) {
-    __shared__ unsigned int hist[SMAXC * SMAXC];
-    for (int i = threadIdx.x; i < C * C; i += 256) hist[i] = 0;
+                                                         int force_coverage, unsigned long long* __restrict__ cm, long long ignore,
+                                                         unsigned long long* __restrict__ skipped) {
+    __shared__ unsigned int hist[SMAXC * SMAXC + 2];
+    for (int i = threadIdx.x; i < C * C + 2; i += 256) hist[i] = 0;
     __syncthreads();
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        int t = (int)yt[i], p = (int)yp[i];
-        if (force_coverage && i < C) { t = (int)i; p = (int)i; }
-        if ((unsigned)t < (unsigned)C && (unsigned)p < (unsigned)C) atomicAdd(&hist[t * C + p], 1u);
+        if constexpr (IGN) {
+            long long tl = (long long)yt[i];
+            int p = (int)yp[i];
+            if (force_coverage && i < C) { tl = i; p = (int)i; }
+            if (tl == ignore) atomicAdd(&hist[C * C + 1], 1u);
+            else if ((unsigned long long)tl >= (unsigned long long)C) atomicAdd(&hist[C * C], 1u);
+            else if ((unsigned)p < (unsigned)C) atomicAdd(&hist[(int)tl * C + p], 1u);
+        } else {
+            int t = (int)yt[i], p = (int)yp[i];
+            if (force_coverage && i < C) { t = (int)i; p = (int)i; }
+            if ((unsigned)t < (unsigned)C && (unsigned)p < (unsigned)C) atomicAdd(&hist[t * C + p], 1u);
+        }
     }
     __syncthreads();
     for (int i = threadIdx.x; i < C * C; i += 256)
         if (hist[i]) atomicAdd(&cm[i], (unsigned long long)hist[i]);
+    if constexpr (IGN) {
+        if (skipped != nullptr && threadIdx.x < 2 && hist[C * C + threadIdx.x]) atomicAdd(&skipped[threadIdx.x], (unsigned long long)hist[C * C + threadIdx.x]);
+    }
+}
+
+template <bool IGN>
+static void confusion_launch(const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C, int force_coverage,
+                             unsigned long long* cm, long long ignore, unsigned long long* skipped, hipStream_t st) {
+    const int blocks = grid_for(n) < 1024 ? grid_for(n) : 1024;
+    if (true_bytes == 1 && pred_bytes == 1)
+        hipLaunchKernelGGL((confusion_kernel<unsigned char, unsigned char, IGN>), dim3(blocks), dim3(256), 0, st, (const unsigned char*)y_true,
+                           (const unsigned char*)y_pred, n, C, force_coverage, cm, ignore, skipped);
+    else if (true_bytes == 8 && pred_bytes == 1)
+        hipLaunchKernelGGL((confusion_kernel<long long, unsigned char, IGN>), dim3(blocks), dim3(256), 0, st, (const long long*)y_true,
+                           (const unsigned char*)y_pred, n, C, force_coverage, cm, ignore, skipped);
+    else if (true_bytes == 1 && pred_bytes == 8)
+        hipLaunchKernelGGL((confusion_kernel<unsigned char, long long, IGN>), dim3(blocks), dim3(256), 0, st, (const unsigned char*)y_true,
+                           (const long long*)y_pred, n, C, force_coverage, cm, ignore, skipped);
+    else
+        hipLaunchKernelGGL((confusion_kernel<long long, long long, IGN>), dim3(blocks), dim3(256), 0, st, (const long long*)y_true,
+                           (const long long*)y_pred, n, C, force_coverage, cm, ignore, skipped);
 }
 }  // namespace pylc
 
@@ -221,20 +254,17 @@ extern "C" int pylc_confusion_matrix(const void* y_true, int true_bytes, const v
                                      int force_coverage, unsigned long long* cm /* [C*C], zeroed by the caller */, void* stream) {
     PYLC_REQUIRE(y_true && y_pred && cm && n > 0 && C >= 2 && C <= SMAXC, "confusion_matrix: bad arguments");
     PYLC_REQUIRE((true_bytes == 1 || true_bytes == 8) && (pred_bytes == 1 || pred_bytes == 8), "confusion_matrix: masks must be uint8 or int64");
-    const int blocks = grid_for(n) < 1024 ? grid_for(n) : 1024;
-    hipStream_t st = as_stream(stream);
-    if (true_bytes == 1 && pred_bytes == 1)
-        hipLaunchKernelGGL((confusion_kernel<unsigned char, unsigned char>), dim3(blocks), dim3(256), 0, st, (const unsigned char*)y_true,
-                           (const unsigned char*)y_pred, n, C, force_coverage, cm);
-    else if (true_bytes == 8 && pred_bytes == 1)
-        hipLaunchKernelGGL((confusion_kernel<long long, unsigned char>), dim3(blocks), dim3(256), 0, st, (const long long*)y_true,
-                           (const unsigned char*)y_pred, n, C, force_coverage, cm);
-    else if (true_bytes == 1 && pred_bytes == 8)
-        hipLaunchKernelGGL((confusion_kernel<unsigned char, long long>), dim3(blocks), dim3(256), 0, st, (const unsigned char*)y_true,
-                           (const long long*)y_pred, n, C, force_coverage, cm);
-    else
-        hipLaunchKernelGGL((confusion_kernel<long long, long long>), dim3(blocks), dim3(256), 0, st, (const long long*)y_true,
-                           (const long long*)y_pred, n, C, force_coverage, cm);
+    confusion_launch<false>(y_true, true_bytes, y_pred, pred_bytes, n, C, force_coverage, cm, 0, nullptr, as_stream(stream));
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_confusion_matrix_ex(const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C,
+                                        int force_coverage, unsigned long long* cm /* [C*C], zeroed by the caller */, int ignore_index,
+                                        unsigned long long* n_skipped /* [2]: bad, ignored; ADDED into; may be NULL */, void* stream) {
+    PYLC_REQUIRE(y_true && y_pred && cm && n > 0 && C >= 2 && C <= SMAXC, "confusion_matrix_ex: bad arguments");
+    PYLC_REQUIRE((true_bytes == 1 || true_bytes == 8) && (pred_bytes == 1 || pred_bytes == 8), "confusion_matrix_ex: masks must be uint8 or int64");
+    confusion_launch<true>(y_true, true_bytes, y_pred, pred_bytes, n, C, force_coverage, cm, (long long)ignore_index, n_skipped, as_stream(stream));
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
 }

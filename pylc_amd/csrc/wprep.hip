@@ -11,7 +11,7 @@ typedef _Float16 f16;
 __device__ __forceinline__ float wprep_scale(unsigned amax_bits) {      // = conv_igemm.hip pow2_scale_for
     int e = (int)((amax_bits >> 23) & 0xFFu);
     int se = 127 + 14 - (e - 127);
-    se = se < 1 ? 1 : (se > 253 ? 253 : se);
+    se = se < 1 ? 1 : (se > 242 ? 242 : se);
     return __uint_as_float((unsigned)se << 23);
 }
 

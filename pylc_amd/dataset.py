@@ -195,26 +195,44 @@ def oversample_layout(rates):
 class Extracted:
     """extract_photo's output.  img: device uint8 [n,C,t,t]; mask: device uint8 [n,t,t] class indices or None; sums: device int64
     [n,2,C] (per tile and channel, sum x and sum x^2); hist: device int64 [n, n_classes + 1] or None (the last bin, values >= n_classes,
-    is all zero: extract_photo raises otherwise); geometry: the reference's meta.extract fields (photo.fit_geometry's, plus n)."""
+    is all zero: extract_photo raises otherwise -- or, with ignore_index, counts exactly the pixels that hold it); geometry: the
+    reference's meta.extract fields (photo.fit_geometry's, plus n)."""
 
-    def __init__(self, img, mask, sums, hist, geometry, tile, stride, n_classes):
+    def __init__(self, img, mask, sums, hist, geometry, tile, stride, n_classes, ignore_index=None):
         self.img, self.mask, self.sums, self.hist, self.geometry = img, mask, sums, hist, geometry
-        self.tile, self.stride, self.n_classes = tile, stride, n_classes
+        self.tile, self.stride, self.n_classes, self.ignore_index = tile, stride, n_classes, ignore_index
 
 
-def _check_bad_classes(hist, n_classes):
+def _check_ignore_index(ignore_index, n_classes):
+    """An ignore label of a uint8 mask: the histograms keep it apart from the classes only in their last bin (values >= n_classes)."""
+    ignore_index = int(ignore_index)
+    if not n_classes <= ignore_index <= 255:
+        raise ValueError('ignore_index=%d must lie in n_classes=%d..255 here: the class histogram cannot separate an ignore value inside the '
+                         'class range, and masks are uint8' % (ignore_index, n_classes))
+    return ignore_index
+
+
+def _check_bad_classes(hist, n_classes, mask=None, ignore_index=None):
     bad = int(hist[:, -1].sum())
+    if ignore_index is not None:
+        ignored = int((mask == ignore_index).sum())          # every value >= n_classes must be the ignore value
+        if bad != ignored:
+            raise ValueError('%d mask pixels hold a class index >= n_classes=%d other than ignore_index=%d' % (bad - ignored, n_classes,
+                                                                                                            ignore_index))
+        return
     if bad:
         raise ValueError('%d mask pixels hold a class index >= n_classes=%d (one_hot in utils/profile.py:109 would raise)' % (bad, n_classes))
 
 
-def extract_photo(image, mask_rgb=None, palette=None, tile=512, stride=None, scale=None, fit=False, n_classes=None, device='cuda'):
+def extract_photo(image, mask_rgb=None, palette=None, tile=512, stride=None, scale=None, fit=False, n_classes=None, device='cuda',
+                  ignore_index=None):
     """One image / mask pair through Extractor.extract (utils/extract.py:133-215): a decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1]
     grayscale uint8) and, optionally, its RGB mask [H,W,3] with the schema palette -> Extracted.
 
     The image is uploaded once, scaled by get_image's arithmetic (photo.scaled_size, INTER_AREA) when `scale` is given, and cut by one
     launch of pylc_extract_tiles.  The mask is nearest-resized to the same scaled size and class-encoded (photo.encode_mask).  stride
-    defaults to the tile (config.py:137); n_classes to the palette's length.
+    defaults to the tile (config.py:137); n_classes to the palette's length.  ignore_index (n_classes..255, not in the reference): a mask
+    colour outside the palette is encoded as this value instead of class 1, and the tiles' last histogram bin counts those pixels.
 
     fit=True applies adjust_to_tile's second resize (photo.fit_image) and is allowed WITHOUT a mask only: the reference fits the image
     but not the mask (extract.py:154-156 against :188-195), so its own image and mask tile counts diverge there.
@@ -231,6 +249,10 @@ def extract_photo(image, mask_rgb=None, palette=None, tile=512, stride=None, sca
         n_classes = len(palette)
     if n_classes is not None:
         n_classes = _check_n_classes(n_classes)
+    if ignore_index is not None:
+        if n_classes is None:
+            raise ValueError('ignore_index needs a mask with its palette')
+        ignore_index = _check_ignore_index(ignore_index, n_classes)
     shape = tuple(image.shape)
     h, w = shape[0], shape[1]
     if fit:
@@ -258,12 +280,12 @@ def extract_photo(image, mask_rgb=None, palette=None, tile=512, stride=None, sca
         img = photo.resize_area(photo._upload_photo(image, device), h_c, w_c)       # at its own size: a relayout to [C,H,W]
     mask = None
     if mask_rgb is not None:
-        mask = photo.encode_mask(mask_rgb, palette, (h_c, w_c), img.device)
+        mask = photo.encode_mask(mask_rgb, palette, (h_c, w_c), img.device, unmatched=1 if ignore_index is None else ignore_index)
     tiles, mtiles, sums, hist = cut_tiles(img, mask, tile, stride, n_classes if mask is not None else None)
     if hist is not None:
-        _check_bad_classes(hist, n_classes)
+        _check_bad_classes(hist, n_classes, mtiles, ignore_index)
     geom = dict(geom, n=rows * cols)
-    return Extracted(tiles, mtiles, sums, hist, geom, tile, stride, n_classes)
+    return Extracted(tiles, mtiles, sums, hist, geom, tile, stride, n_classes, ignore_index)
 
 
 # ---- the profile (host, double arithmetic on exact integers) ---------------------------------------------------------------------
@@ -281,8 +303,12 @@ def m2(p, n_classes):
     return (n_classes / (n_classes - 1)) * (1 - np.sum(p ** 2))
 
 
-def profile_from_sums(sums, hist, tile, n_classes):
+def profile_from_sums(sums, hist, tile, n_classes, ignore=False):
     """get_profile (utils/profile.py:92-148) from per-tile integer sums: sums int [n,2,C] (sum x, sum x^2), hist int [n, n_classes].
+
+    ignore=True (not in the reference): hist is [n, n_classes + 1] and its last bin counts the pixels that carry the ignore label.  px_dist,
+    dset_px_dist, probs, weights, m2 and jsd are then taken over the VALID pixels, dset_px_count is their number and ignored_px_count the
+    others'; px_mean and px_std do not depend on labels and stay as they are.
 
     Per tile and channel, with N = tile^2: mean = S / N and the unbiased std = sqrt((N * SS - S^2) / (N * (N - 1))) -- torch.mean /
     torch.std over (0, 2, 3) of a [1,C,t,t] batch; for one channel the reference pools over the whole tile, which is the same thing.
@@ -307,7 +333,14 @@ def profile_from_sums(sums, hist, tile, n_classes):
     px_dist = hist[:, :n_classes]
     dset_px_dist = np.sum(px_dist, axis=0)
     dset_px_count = np.sum(dset_px_dist)
-    if int(dset_px_count) != n * N:
+    ignored = 0
+    if ignore:
+        if hist.shape[1] != n_classes + 1:
+            raise ValueError('ignore=True needs histograms of n_classes + 1 = %d bins, got %d' % (n_classes + 1, hist.shape[1]))
+        ignored = int(hist[:, n_classes].sum())
+        if int(dset_px_count) == 0:
+            raise ValueError('profile of a tile set without a labelled pixel')
+    if int(dset_px_count) + ignored != n * N:
         raise ValueError('pixel distribution (%d) does not match the tile count (%d x %d)' % (int(dset_px_count), n, N))
     probs = dset_px_dist / dset_px_count
     weights = 1 / (np.log(1.02 + probs))
@@ -317,7 +350,8 @@ def profile_from_sums(sums, hist, tile, n_classes):
     return {'n_samples': n, 'tile_size': int(tile), 'tile_px_count': N, 'ch': c, 'n_classes': int(n_classes),
             'px_mean': (mean.sum(0) / n).tolist(), 'px_std': (std.sum(0) / n).tolist(),
             'px_dist': px_dist.tolist(), 'dset_px_dist': dset_px_dist.tolist(), 'dset_px_count': int(dset_px_count),
-            'probs': probs.tolist(), 'weights': weights.tolist(), 'm2': float(m2(probs, n_classes)), 'jsd': float(jsd(probs, balanced))}
+            'probs': probs.tolist(), 'weights': weights.tolist(), 'm2': float(m2(probs, n_classes)), 'jsd': float(jsd(probs, balanced)),
+            **({'ignored_px_count': ignored} if ignore else {})}
 
 
 def oversample_rates(profile, rate_coef_range=(1, 21), threshold_range=(0, 3.), rate_range=(0, 4), n_samples_ratio=0.36):
@@ -396,18 +430,20 @@ class TileSet:
     """Tiles of one size with their integer statistics, resident on the device (keep='device') or in pinned host memory (keep='host');
     the statistics always end on the host (numpy int64).  add() appends extract_photo's output, from_arrays() takes tiles cut elsewhere
     (their statistics come from pylc_tile_stats), coshuffle() permutes everything alike, partition() is a view, batches() feeds
-    Model.train and profile() is the reference's dataset profile."""
+    Model.train and profile() is the reference's dataset profile.  ignore_index (n_classes..255): masks may hold this value for pixels
+    without a label; the histograms then have a last column with their count per tile, and the profile is taken over the other pixels."""
 
-    def __init__(self, ch, n_classes, tile, keep='device'):
+    def __init__(self, ch, n_classes, tile, keep='device', ignore_index=None):
         if keep not in ('device', 'host'):
             raise ValueError("keep must be 'device' or 'host', got %r" % (keep,))
         if ch not in (1, 3):
             raise ValueError('ch must be 1 or 3, got %s' % ch)
         self.ch, self.n_classes, self.tile, self.keep = int(ch), _check_n_classes(n_classes), int(tile), keep
+        self.ignore_index = None if ignore_index is None else _check_ignore_index(ignore_index, self.n_classes)
         self._own = self                       # partitions share their parent's storage
         self._img, self._mask = [], []         # chunks; _storage() joins them
         self._sums = np.zeros((0, 2, self.ch), np.int64)
-        self._hist = np.zeros((0, self.n_classes), np.int64)
+        self._hist = np.zeros((0, self.n_classes + (0 if self.ignore_index is None else 1)), np.int64)
         self._lo, self._hi = 0.0, 1.0
 
     # -- filling
@@ -426,11 +462,15 @@ class TileSet:
         sums = np.asarray(sums.cpu() if torch.is_tensor(sums) else sums, dtype=np.int64).reshape(n, 2, self.ch)
         if hist is not None:
             hist = np.asarray(hist.cpu() if torch.is_tensor(hist) else hist, dtype=np.int64).reshape(n, -1)
-            if hist.shape[1] == self.n_classes + 1:
+            if self.ignore_index is not None:
+                if hist.shape[1] != self.n_classes + 1:
+                    raise ValueError('histograms of %d bins in a set of %d classes with an ignore label' % (hist.shape[1], self.n_classes))
+                _check_bad_classes(hist, self.n_classes, mask, self.ignore_index)
+            elif hist.shape[1] == self.n_classes + 1:
                 if hist[:, -1].any():
                     raise ValueError('%d mask pixels hold a class index >= n_classes=%d' % (int(hist[:, -1].sum()), self.n_classes))
                 hist = hist[:, :self.n_classes]
-            if hist.shape[1] != self.n_classes:
+            if hist.shape[1] != self._hist.shape[1]:
                 raise ValueError('histograms of %d bins in a set of %d classes' % (hist.shape[1], self.n_classes))
             self._hist = np.concatenate([self._hist, hist])
         self._sums = np.concatenate([self._sums, sums])
@@ -454,6 +494,8 @@ class TileSet:
             raise ValueError('tiles of %d in a set of %d' % (extracted.tile, self.tile))
         if extracted.mask is not None and extracted.n_classes != self.n_classes:
             raise ValueError('tiles of %s classes in a set of %d' % (extracted.n_classes, self.n_classes))
+        if extracted.mask is not None and getattr(extracted, 'ignore_index', None) not in (None, self.ignore_index):
+            raise ValueError('tiles with ignore_index=%s in a set with %s' % (extracted.ignore_index, self.ignore_index))
         return self._append(extracted.img, extracted.mask, extracted.sums, extracted.hist)
 
     def from_arrays(self, img, mask=None, sums=None, hist=None, device='cuda'):
@@ -543,7 +585,7 @@ class TileSet:
         if not 0 <= lo <= hi <= 1:
             raise ValueError('partition (%s, %s) outside 0 <= lo <= hi <= 1' % (lo, hi))
         view = object.__new__(TileSet)
-        view.ch, view.n_classes, view.tile, view.keep = self.ch, self.n_classes, self.tile, self.keep
+        view.ch, view.n_classes, view.tile, view.keep, view.ignore_index = self.ch, self.n_classes, self.tile, self.keep, self.ignore_index
         view._own = self._own
         span = self._hi - self._lo
         view._lo, view._hi = self._lo + lo * span, self._lo + hi * span
@@ -569,8 +611,9 @@ class TileSet:
             raise ValueError('oversampling needs masks: the rates come from their class histograms')
         if chunk <= 0:
             raise ValueError('chunk=%s' % chunk)
-        out = TileSet(self.ch, self.n_classes, self.tile, self.keep)
+        out = TileSet(self.ch, self.n_classes, self.tile, self.keep, self.ignore_index)
         img, mask = self.img, self.mask
+        pad = 1 if self.ignore_index is None else 0         # (with an ignore label the stored histograms have the last bin already)
         for lo in range(0, n, chunk):
             hi = min(lo + chunk, n)
             sel = (src >= lo) & (src < hi)
@@ -584,7 +627,7 @@ class TileSet:
             pick = np.where(aug, (hi - lo) + np.cumsum(aug) - 1, c_src)
             idx = torch.from_numpy(pick).to(a_img.device)
             sums = np.concatenate([self.sums[lo:hi], a_sums.cpu().numpy()])[pick]
-            hist = np.concatenate([np.pad(self.hist[lo:hi], ((0, 0), (0, 1))), a_hist.cpu().numpy()])[pick]
+            hist = np.concatenate([np.pad(self.hist[lo:hi], ((0, 0), (0, pad))), a_hist.cpu().numpy()])[pick]
             out._append(torch.cat([d_img, a_img]).index_select(0, idx), torch.cat([d_mask, a_mask]).index_select(0, idx), sums, hist)
         return out
 
@@ -593,4 +636,4 @@ class TileSet:
         up px_mean, px_std and weights.  Note px_std: the mean over tiles of the per-tile std, not the dataset's."""
         if self.hist is None:
             raise ValueError('a profile needs masks')
-        return profile_from_sums(self.sums, self.hist, self.tile, self.n_classes)
+        return profile_from_sums(self.sums, self.hist, self.tile, self.n_classes, ignore=self.ignore_index is not None)

@@ -185,6 +185,7 @@ SIGNATURES = {
     'pylc_stitch_overlap_argmax': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     'pylc_resize_area_u8': (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
     'pylc_class_encode_resize': (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P]),
+    'pylc_class_encode_resize_ex': (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _I, _P]),
     'pylc_image_pack_tiles_ex': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     'pylc_image_pack_denom': (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _F, _P, _P]),
     'pylc_image_pack_u8': (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
@@ -192,13 +193,18 @@ SIGNATURES = {
     'pylc_tile_stats': (_I, [_P, _LL, _I, _I, _P, _I, _I, _P, _P, _P]),
     'pylc_augment_tiles': (_I, [_P, _P, _LL, _I, _I, _P, _P, _P, _LL, _I, _P, _P, _I, _P, _P, _P]),
     'pylc_confusion_matrix': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P]),
+    'pylc_confusion_matrix_ex': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _I, _P, _P]),
     'pylc_logits_score': (_I, [_P, _I, _P, _I, _LL, _I, _P, _P, _P]),
+    'pylc_logits_score_ex': (_I, [_P, _I, _P, _I, _LL, _I, _P, _I, _P, _P]),
     'pylc_nhwc_to_nchw': (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     'pylc_nchw_to_nhwc': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'pylc_multiloss_workspace_floats': (_SZ, [_LL, _I]),
     'pylc_multiloss_stats': (_I, [_P, _I, _P, _LL, _I, _P, _P, _P, _P]),
     'pylc_multiloss_finalize': (_I, [_P, _D, _I, _F, _F, _F, _P, _P]),
     'pylc_multiloss_bwd': (_I, [_P, _I, _P, _LL, _I, _P, _P, _D, _F, _F, _F, _P, _P, _I, _P, _P]),
+    'pylc_multiloss_stats_ex': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P, _P, _P, _P]),
+    'pylc_multiloss_finalize_ex': (_I, [_P, _I, _F, _F, _F, _P, _P]),
+    'pylc_multiloss_bwd_ex': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P, _F, _F, _F, _P, _P, _I, _P, _P]),
     'pylc_sqnorm_workspace_floats': (_SZ, [_LL]),
     'pylc_grad_norm_clip': (_I, [_P, _LL, _F, _P, _P, _P]),
     'pylc_adamw_step': (_I, [_P, _P, _P, _P, _LL, _P, _F, _F, _F, _F, _F, _I, _P]),

@@ -9,13 +9,19 @@ from .runtime import runtime
 
 
 class MultiLoss(nn.Module):
-    """MultiLoss(loss_weights={'weighted','weights','ce','dice','focal'}, schema={'n_classes','class_codes','class_labels'}).
+    """MultiLoss(loss_weights={'weighted','weights','ce','dice','focal'}, schema={'n_classes','class_codes','class_labels'}, ignore_index=None).
+
+    ignore_index (an int, not in the reference): pixels whose target equals it are left out of all three terms and get a zero gradient;
+    targets may then be uint8 or int64.  Any other target outside 0..n_classes-1 is skipped too and counted in `.bad_targets` (an int64
+    [1] device tensor, read by Model.log).
 
     forward(pred, target) -> 0-d tensor (ce_w*CE + dice_w*Dice + focal_w*Focal) with grad; side effects
     .ce / .dsc / .fl hold the three terms (loss.py:107-112).  One kernel pass computes all three."""
 
-    def __init__(self, loss_weights, schema):
+    def __init__(self, loss_weights, schema, ignore_index=None):
         super().__init__()
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.bad_targets = None
         self.n_classes = schema['n_classes']
         self.codes = schema.get('class_codes')
         self.categories = schema.get('class_labels')
@@ -45,7 +51,11 @@ class MultiLoss(nn.Module):
     def _all(self, pred, target, w_ce, w_d, w_f):
         self._check(pred, target)
         cw = self.weights if self.weighted else None
-        return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group)
+        if self.ignore_index is None:
+            return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group)
+        if self.bad_targets is None or self.bad_targets.device != pred.device:
+            self.bad_targets = torch.zeros(1, dtype=torch.int64, device=pred.device)
+        return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group, self.ignore_index, self.bad_targets)
 
     def forward(self, pred, target):
         losses = self._all(pred, target, self.ce_weight, self.dsc_weight, self.fl_weight)

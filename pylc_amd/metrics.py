@@ -9,8 +9,10 @@ from . import lib as L
 from .lib import lib, check, ptr, stream
 
 
-def confusion_matrix(y_true, y_pred, n_classes, force_coverage=True):
-    """int64 [n_classes, n_classes] counts (device) for uint8 / int64 masks of equal size."""
+def confusion_matrix(y_true, y_pred, n_classes, force_coverage=True, ignore_index=None, skipped=None):
+    """int64 [n_classes, n_classes] counts (device) for uint8 / int64 masks of equal size.  With ignore_index, pixels whose true label
+    equals it or lies outside 0..n_classes-1 are left out; `skipped` (int64 [2] device tensor, optional) has their numbers (out of
+    range, ignored) ADDED into it."""
     L.init()
     yt, yp = y_true.contiguous().reshape(-1), y_pred.contiguous().reshape(-1)
     if yt.numel() != yp.numel():
@@ -19,8 +21,16 @@ def confusion_matrix(y_true, y_pred, n_classes, force_coverage=True):
         if t.dtype not in (torch.uint8, torch.int64):
             raise TypeError('masks must be uint8 or int64 class indices, got %s' % t.dtype)
     cm = torch.zeros(n_classes * n_classes, device=yt.device, dtype=torch.int64)
-    check(lib.pylc_confusion_matrix(ptr(yt), yt.element_size(), ptr(yp), yp.element_size(), yt.numel(), n_classes,
-                                    int(force_coverage), ptr(cm), stream()))
+    if ignore_index is None:
+        if skipped is not None:
+            raise ValueError('skipped counts need an ignore_index')
+        check(lib.pylc_confusion_matrix(ptr(yt), yt.element_size(), ptr(yp), yp.element_size(), yt.numel(), n_classes,
+                                        int(force_coverage), ptr(cm), stream()))
+    else:
+        if skipped is not None and (skipped.dtype != torch.int64 or skipped.numel() != 2 or not skipped.is_contiguous()):
+            raise ValueError('skipped must be a contiguous int64 tensor of 2 entries')
+        check(lib.pylc_confusion_matrix_ex(ptr(yt), yt.element_size(), ptr(yp), yp.element_size(), yt.numel(), n_classes,
+                                           int(force_coverage), ptr(cm), int(ignore_index), ptr(skipped), stream()))
     return cm.view(n_classes, n_classes)
 
 
@@ -37,18 +47,20 @@ def scores(cm):
     return {'f1': float((f1 * w).sum() / w.sum()), 'iou': float((iou * w).sum() / w.sum()), 'mcc': float(mcc), 'cmatrix': norm}
 
 
-def evaluate(y_true, y_pred, n_classes):
-    """Evaluator.evaluate() (utils/evaluate.py:131-148) minus the plotting / report printing."""
-    return scores(confusion_matrix(y_true, y_pred, n_classes, force_coverage=True))
+def evaluate(y_true, y_pred, n_classes, ignore_index=None):
+    """Evaluator.evaluate() (utils/evaluate.py:131-148) minus the plotting / report printing; with ignore_index, over the pixels whose true
+    label is a class other than it."""
+    return scores(confusion_matrix(y_true, y_pred, n_classes, force_coverage=True, ignore_index=ignore_index))
 
 
 # ---- validation scores while training: logits -> counts in one launch (csrc/score.hip, DESIGN.md section 5.7) ---------------------------
-def logits_confusion(logits, target=None, counts=None, return_mask=False):
+def logits_confusion(logits, target=None, counts=None, return_mask=False, ignore_index=None):
     """Confusion counts (and / or the class mask) of a batch of logits [B,C,H,W] as a net returns them, in ONE launch and without a host
     synchronisation: the class of a pixel is the first maximum of its logits (numpy's argmax).  target [B,H,W], uint8 or int64 class
     indices: counts[t * C + p] += 1, and counts[C * C] counts the pixels whose target lies outside 0..C-1.  `counts` (int64 [C*C + 1],
     device) is ADDED into; a zeroed one is allocated when none is passed.  Returns counts (None without a target), or (counts, mask) with
-    return_mask, mask uint8 [B,H,W]."""
+    return_mask, mask uint8 [B,H,W].  With ignore_index, counts has C*C + 2 entries: a target equal to the index adds to counts[C*C + 1]
+    (and not to the matrix, even for an index inside 0..C-1), counts[C*C] keeps the other out-of-range ones."""
     from . import ops
     L.init()
     if logits.dim() != 4:
@@ -69,12 +81,16 @@ def logits_confusion(logits, target=None, counts=None, return_mask=False):
             raise ValueError('target %s does not match logits %s' % (tuple(target.shape), tuple(logits.shape)))
         target = target.to(x.device, non_blocking=True).contiguous()
         tbytes = target.element_size()
+        cells = c * c + (1 if ignore_index is None else 2)
         if counts is None:
-            counts = torch.zeros(c * c + 1, device=x.device, dtype=torch.int64)
-        elif counts.dtype != torch.int64 or counts.numel() != c * c + 1 or not counts.is_contiguous():
-            raise ValueError('counts must be a contiguous int64 tensor of %d entries' % (c * c + 1))
+            counts = torch.zeros(cells, device=x.device, dtype=torch.int64)
+        elif counts.dtype != torch.int64 or counts.numel() != cells or not counts.is_contiguous():
+            raise ValueError('counts must be a contiguous int64 tensor of %d entries' % cells)
     mask = torch.empty((b, h, w), device=x.device, dtype=torch.uint8) if return_mask else None
-    check(lib.pylc_logits_score(ptr(x), pitch, ptr(target), tbytes, n, c, ptr(mask), ptr(counts), stream()))
+    if ignore_index is None or target is None:
+        check(lib.pylc_logits_score(ptr(x), pitch, ptr(target), tbytes, n, c, ptr(mask), ptr(counts), stream()))
+    else:
+        check(lib.pylc_logits_score_ex(ptr(x), pitch, ptr(target), tbytes, n, c, ptr(mask), int(ignore_index), ptr(counts), stream()))
     return (counts, mask) if return_mask else counts
 
 
@@ -92,27 +108,28 @@ class ScoreLog:
     """Validation scores next to the loss log: add() accumulates the confusion counts of every validation batch on the device (one launch,
     no host read), close() turns them into one row per validation pass -- the only D2H copy -- and tracks the best weighted IoU."""
 
-    def __init__(self, n_classes):
+    def __init__(self, n_classes, ignore_index=None):
         self.n_classes = int(n_classes)
-        self.counts = None                 # int64 [C*C + 1], allocated where the first logits live
+        self.ignore_index = None if ignore_index is None else int(ignore_index)      # targets equal to it are dropped and reported as 'ignored'
+        self.counts = None                 # int64 [C*C + 1] (+ 1 with an ignore label), allocated where the first logits live
         self.last_counts = None            # host int64 [C,C] of the last closed pass (summed over the group)
         self.rows = []
         self.best_iou, self.is_best = 0.0, False
 
     def _zeros(self, device):
-        return torch.zeros(self.n_classes * self.n_classes + 1, device=device, dtype=torch.int64)
+        return torch.zeros(self.n_classes * self.n_classes + (1 if self.ignore_index is None else 2), device=device, dtype=torch.int64)
 
     def add(self, logits, target):
         if logits.shape[1] != self.n_classes:
             raise ValueError('ScoreLog of %d classes got logits with %d' % (self.n_classes, logits.shape[1]))
         if self.counts is None:
             self.counts = self._zeros(logits.device)
-        logits_confusion(logits, target, counts=self.counts)
+        logits_confusion(logits, target, counts=self.counts, ignore_index=self.ignore_index)
 
     def close(self, it, epoch, group=None):
         """End of a validation pass: the counts (summed over `group` when given -- a collective every rank must reach) become a row
-        {'iter', 'epoch', 'f1', 'iou', 'mcc', 'class_iou', 'class_f1', 'support'}; the device counts are zeroed for the next pass.
-        Returns the row, or None when no pixel was added."""
+        {'iter', 'epoch', 'f1', 'iou', 'mcc', 'class_iou', 'class_f1', 'support'} (with an ignore label also 'ignored', the number of
+        dropped pixels); the device counts are zeroed for the next pass.  Returns the row, or None when no valid pixel was added."""
         c = self.n_classes
         if self.counts is None:
             self.counts = self._zeros('cpu')           # a rank that saw no batch still takes part in the collective
@@ -132,6 +149,8 @@ class ScoreLog:
         s, pc = scores(cm), per_class(cm)
         row = {'iter': int(it), 'epoch': int(epoch), 'f1': s['f1'], 'iou': s['iou'], 'mcc': s['mcc'],
                'class_iou': [float(v) for v in pc['iou']], 'class_f1': [float(v) for v in pc['f1']], 'support': [int(v) for v in pc['support']]}
+        if self.ignore_index is not None:
+            row['ignored'] = int(host[c * c + 1])
         self.rows.append(row)
         self.is_best = row['iou'] > self.best_iou
         if self.is_best:

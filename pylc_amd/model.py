@@ -52,6 +52,7 @@ class Meta:
         self.report = 20                   # config.py:240
         self.pretrained = False
         self.freeze_bn = False             # fine-tuning: BatchNorms keep their running statistics in training steps (DeepLab(freeze_bn=True))
+        self.ignore_index = None           # an int (255 for uint8 masks): pixels with this label are left out of the loss and the scores
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise AttributeError('unknown Meta field %r' % k)
@@ -193,7 +194,11 @@ class Model:
         self.crit = MultiLoss(
             loss_weights={'weighted': m.weighted, 'weights': m.weights, 'ce': m.ce_weight, 'dice': m.dice_weight,
                           'focal': m.focal_weight},
-            schema={'n_classes': m.n_classes, 'class_codes': m.class_codes, 'class_labels': m.class_labels}).to(self.device)
+            schema={'n_classes': m.n_classes, 'class_codes': m.class_codes, 'class_labels': m.class_labels},
+            ignore_index=m.ignore_index).to(self.device)
+        ign = None if m.ignore_index is None else int(m.ignore_index)
+        if self.scores is not None and self.scores.ignore_index != ign:
+            self.scores.ignore_index, self.scores.counts = ign, None          # (the counts gain or lose the cell of the ignored pixels)
         self.init_optim()
         return self
 
@@ -233,6 +238,14 @@ class Model:
         mean, std, denom = self._stats(default)
         return ops.image_pack(x, mean, std, denom)
 
+    def _target(self, y):
+        """The target batch on the device, cropped.  int64 for the plain loss head; with Meta.ignore_index a uint8 batch (as the tile sets
+        hold it) goes through as it is: the loss and score kernels read bytes."""
+        y = y.to(self.device, non_blocking=True)
+        if self.meta.ignore_index is None or y.dtype != torch.uint8:
+            y = y.long()
+        return self.crop_target(y)
+
     def crop_target(self, y):
         if self.meta.arch == 'unet':
             p = self.meta.pad_size
@@ -248,7 +261,7 @@ class Model:
                              'taken from batch statistics, which a frozen BatchNorm does not compute')
         self._ranges_checked = False
         x4 = self.pack_input(x)
-        y = self.crop_target(y.to(self.device, non_blocking=True).long())
+        y = self._target(y)
         y_hat = self.net(x4)
         loss = self.crit(y_hat, y)
         self.loss.push(torch.stack((self.crit.ce, self.crit.dsc, self.crit.fl)))
@@ -285,11 +298,13 @@ class Model:
         self.net.eval()
         self._refresh_for_inference()
         x4 = self.pack_input(x)
-        y = self.crop_target(y.to(self.device, non_blocking=True).long())
+        y = self._target(y)
         with torch.no_grad():
             y_hat = self.net(x4)
             self.loss.push(self.crit.all_losses(y_hat, y)[1:4])
             if self.scores is not None:
+                if self.scores.ignore_index != self.meta.ignore_index:
+                    raise ValueError('Model.scores has ignore_index=%r, Meta has %r' % (self.scores.ignore_index, self.meta.ignore_index))
                 self.scores.add(y_hat, y)
         return [y_hat]
 
@@ -318,6 +333,13 @@ class Model:
             ops.check_equal_shards()
         training = self.net.training
         self.loss.log(self.iter, training)
+        bad = getattr(self.crit, 'bad_targets', None)
+        if bad is not None:                 # (next to the loss log's device read: once per report interval, never per step)
+            n_bad = int(bad.item())
+            if n_bad:
+                bad.zero_()
+                raise ValueError('%d targets since the last report lie outside 0..%d and are not ignore_index=%d'
+                                 % (n_bad, self.meta.n_classes - 1, self.meta.ignore_index))
         if self._best_by == 'iou' and self.scores is None:
             raise ValueError("best_by='iou' needs Model.scores (a metrics.ScoreLog)")
         if not training and self.scores is not None:

@@ -442,15 +442,23 @@ def check_equal_shards():
 
 
 class MultiLossFn(torch.autograd.Function):
-    """Returns a [4] tensor (total, ce, dice, focal); only total carries gradient."""
+    """Returns a [4] tensor (total, ce, dice, focal); only total carries gradient.
+
+    ignore_index (an int; None: the plain path): targets may be uint8 or int64, pixels whose target equals the index or lies outside
+    0..C-1 are skipped (pylc_multiloss_*_ex) and the number of valid pixels is read on the device from the
+    (all-reduced) statistics.  bad: an int64 [1] device tensor that the number of out-of-range targets other than the index is ADDED
+    into (optional)."""
 
     @staticmethod
-    def forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group):
+    def forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index=None, bad=None):
         L.init()
         logits = as_nhwc(logits)
         b, c, h, w = logits.shape
         n = b * h * w
         target = target.contiguous()
+        ctx.ignore = ignore_index
+        if ignore_index is not None:
+            return MultiLossFn._forward_ignore(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, int(ignore_index), bad)
         if target.dtype != torch.int64 or tuple(target.shape) != (b, h, w):
             raise L.PylcError('target must be int64 [B,H,W] matching the logits')
         dev = logits.device
@@ -476,6 +484,31 @@ class MultiLossFn(torch.autograd.Function):
         return losses
 
     @staticmethod
+    def _forward_ignore(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad):
+        b, c, h, w = logits.shape
+        n = b * h * w
+        if target.dtype not in (torch.uint8, torch.int64) or tuple(target.shape) != (b, h, w):
+            raise L.PylcError('target must be uint8 or int64 [B,H,W] matching the logits')
+        if bad is not None and (bad.dtype != torch.int64 or bad.numel() != 1 or bad.device != logits.device):
+            raise L.PylcError('bad must be an int64 [1] tensor on the device of the logits')
+        dev = logits.device
+        st = stream()
+        k = 3 + 3 * c
+        stats = torch.empty(k + (2 if group is not None else 0), device=dev)         # (the shard pair rides along as on the plain path)
+        ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
+        check(lib.pylc_multiloss_stats_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
+                                          ptr(class_weights), ptr(stats), ptr(ws), ptr(bad), st))
+        if group is not None:
+            stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
+            _runtime.sync_all_reduce(stats, group)
+            note_shard_pair(stats[k:], dist.get_world_size(group))
+        losses = torch.empty(4, device=dev)
+        check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))      # n_valid: from the reduced class counts
+        ctx.save_for_backward(logits, target, stats, class_weights)
+        ctx.cfg = (None, w_ce, w_dice, w_focal, group)
+        return losses
+
+    @staticmethod
     def backward(ctx, dlosses):
         logits, target, stats, cw = ctx.saved_tensors
         n_global, w_ce, w_dice, w_focal, group = ctx.cfg
@@ -487,15 +520,20 @@ class MultiLossFn(torch.autograd.Function):
         cp = _r4(c)
         dl = empty_nhwc(b, c, h, w, logits.device, cp)
         amax = torch.empty(1, dtype=torch.int32, device=logits.device) if ranges_needed() and _runtime.fused_grad_ranges else None
-        check(lib.pylc_multiloss_bwd(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(cw), ptr(stats), n_global,
-                                     w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
+        ignore = getattr(ctx, 'ignore', None)
+        if ignore is None:
+            check(lib.pylc_multiloss_bwd(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(cw), ptr(stats), n_global,
+                                         w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
+        else:
+            check(lib.pylc_multiloss_bwd_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw),
+                                            ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
         if amax is not None:
             tag_amax(dl, amax)              # (read by a conv backward directly when the net has no logits up-sampling: the U-Net)
-        return dl, None, None, None, None, None, None
+        return dl, None, None, None, None, None, None, None, None
 
 
-def multiloss(logits, target, class_weights, w_ce, w_dice, w_focal, group=None):
-    return MultiLossFn.apply(logits, target, class_weights, w_ce, w_dice, w_focal, group)
+def multiloss(logits, target, class_weights, w_ce, w_dice, w_focal, group=None, ignore_index=None, bad=None):
+    return MultiLossFn.apply(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad)
 
 
 __all__ = [n for n in dir() if not n.startswith('__')]      # everything, underscore helpers included: the package re-exports it (pylc_amd/ops/__init__.py)

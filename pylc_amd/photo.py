@@ -120,10 +120,18 @@ def _palette_tensor(palette, n_min, device):
     return pal.to(device).contiguous()
 
 
-def encode_mask(rgb, palette, out_hw=None, device=None):
+def encode_mask(rgb, palette, out_hw=None, device=None, unmatched=1, ignore_index=None):
     """class_encode of an RGB mask [H,W,3] (uint8, numpy or tensor, host or device) through `palette` ([n][3]), nearest-resized to
-    out_hw = (oh, ow) first (cv2.INTER_NEAREST; default: its own size).  The last matching palette index wins, unmatched colours give 1
-    (utils/tools.py:412-449).  For a ground truth, out_hw is the photograph's (h_scaled, w_scaled).  Returns device uint8 [oh, ow]."""
+    out_hw = (oh, ow) first (cv2.INTER_NEAREST; default: its own size).  The last matching palette index wins, unmatched colours give
+    `unmatched`: 1 as in the reference (utils/tools.py:412-449), any int 0..255, or 'ignore' for the value of `ignore_index`.  For a
+    ground truth, out_hw is the photograph's (h_scaled, w_scaled).  Returns device uint8 [oh, ow]."""
+    if isinstance(unmatched, str):
+        if unmatched != 'ignore' or ignore_index is None:
+            raise ValueError("unmatched is an int 0..255, or 'ignore' together with an ignore_index")
+        unmatched = ignore_index
+    unmatched = int(unmatched)
+    if not 0 <= unmatched <= 255:
+        raise ValueError('unmatched=%d does not fit a uint8 mask (0..255)' % unmatched)
     L.init()
     dev = device or (rgb.device if torch.is_tensor(rgb) and rgb.is_cuda else torch.device('cuda'))
     t = _upload_photo(rgb, dev)
@@ -133,7 +141,10 @@ def encode_mask(rgb, palette, out_hw=None, device=None):
     oh, ow = out_hw if out_hw is not None else (h, w)
     pal = _palette_tensor(palette, 1, dev)
     out = torch.empty((oh, ow), device=dev, dtype=torch.uint8)
-    check(lib.pylc_class_encode_resize(ptr(t), h, w, ptr(pal), pal.shape[0], ptr(out), oh, ow, stream()))
+    if unmatched == 1:
+        check(lib.pylc_class_encode_resize(ptr(t), h, w, ptr(pal), pal.shape[0], ptr(out), oh, ow, stream()))
+    else:
+        check(lib.pylc_class_encode_resize_ex(ptr(t), h, w, ptr(pal), pal.shape[0], ptr(out), oh, ow, unmatched, stream()))
     return out
 
 
@@ -261,8 +272,10 @@ class PhotoEvaluator:
     aggregate() is the --aggregate_metrics result, where validate() overwrites the first C pixels of the CONCATENATION only
     (utils/evaluate.py:150-176): the first image's counts with that coverage, every later image's without."""
 
-    def __init__(self, n_classes, palette):
+    def __init__(self, n_classes, palette, ignore_index=None):
         self.n_classes = int(n_classes)
+        # with an ignore label (0..255) a ground-truth colour outside the palette is encoded as it, and only the other pixels are scored
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
         self.palette = np.asarray(palette, dtype=np.uint8).reshape(-1, 3)
         if self.palette.shape[0] != self.n_classes:
             raise ValueError('palette has %d entries for %d classes' % (self.palette.shape[0], self.n_classes))
@@ -278,12 +291,13 @@ class PhotoEvaluator:
         if (h_s, w_s) != (g['h_scaled'], g['w_scaled']):
             raise ValueError('ground truth mask dims (%dpx x %dpx) do not match predicted mask dims (%dpx x %dpx)' % (w_s, h_s, g['w_scaled'],
                                                                                                                     g['h_scaled']))
-        y_true = encode_mask(gt_rgb, self.palette, (h_s, w_s), result.mask.device)
+        ign = self.ignore_index
+        y_true = encode_mask(gt_rgb, self.palette, (h_s, w_s), result.mask.device, unmatched=1 if ign is None else ign)
         y_pred = result.mask
         if y_pred.shape != y_true.shape:
             raise ValueError('predicted mask %s vs ground truth %s' % (tuple(y_pred.shape), tuple(y_true.shape)))
-        cm = metrics.confusion_matrix(y_true, y_pred, self.n_classes, force_coverage=True)
-        plain = None if self.cm is None else metrics.confusion_matrix(y_true, y_pred, self.n_classes, force_coverage=False)
+        cm = metrics.confusion_matrix(y_true, y_pred, self.n_classes, force_coverage=True, ignore_index=ign)
+        plain = None if self.cm is None else metrics.confusion_matrix(y_true, y_pred, self.n_classes, force_coverage=False, ignore_index=ign)
         return self.add_counts(cm, plain)
 
     def add_counts(self, cm_coverage, cm_plain=None):

@@ -431,6 +431,52 @@ def _ml_bwd(ctx, dlosses, _dstats):
 torch.library.register_autograd('pylc_hip::multiloss', _ml_bwd, setup_context=_ml_setup)
 
 
+# The same with an ignore label (not in the reference): target uint8 or int64, pixels whose target equals
+# ignore_index or lies outside 0..C-1 are skipped.  Returns (losses, stats, bad): bad is an int64 [1] count of the out-of-range targets
+# other than the index.
+@torch.library.custom_op('pylc_hip::multiloss_ignore', mutates_args=())
+def multiloss_ignore(logits: Tensor, target: Tensor, class_weights: Optional[Tensor], w_ce: float, w_dice: float, w_focal: float,
+                     ignore_index: int) -> Tuple[Tensor, Tensor, Tensor]:
+    ctx = _Ctx((True,))
+    bad = torch.zeros(1, dtype=torch.int64, device=logits.device)
+    losses = ops.MultiLossFn.forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, None, ignore_index, bad)
+    return losses, ctx.saved_tensors[2], bad
+
+
+@multiloss_ignore.register_fake
+def _(logits, target, class_weights, w_ce, w_dice, w_focal, ignore_index):
+    return logits.new_empty(4), logits.new_empty(3 + 3 * logits.shape[1]), logits.new_empty(1, dtype=torch.int64)
+
+
+@torch.library.custom_op('pylc_hip::multiloss_ignore_backward', mutates_args=())
+def multiloss_ignore_backward(dlosses: Tensor, logits: Tensor, target: Tensor, stats: Tensor, class_weights: Optional[Tensor], w_ce: float,
+                              w_dice: float, w_focal: float, ignore_index: int) -> Tensor:
+    ctx = _Ctx((True,))
+    ctx.save_for_backward(ops.as_nhwc(logits), target.contiguous(), stats, class_weights)
+    ctx.cfg = (None, w_ce, w_dice, w_focal, None)
+    ctx.ignore = ignore_index
+    return ops.MultiLossFn.backward(ctx, dlosses)[0]
+
+
+@multiloss_ignore_backward.register_fake
+def _(dlosses, logits, target, stats, class_weights, w_ce, w_dice, w_focal, ignore_index):
+    return torch.empty_like(logits)
+
+
+def _mli_setup(ctx, inputs, output):
+    logits, target, cw, w_ce, w_dice, w_focal, ignore_index = inputs
+    ctx.save_for_backward(logits, target, output[1], cw)
+    ctx.w = (w_ce, w_dice, w_focal, ignore_index)
+
+
+def _mli_bwd(ctx, dlosses, _dstats, _dbad):
+    logits, target, stats, cw = ctx.saved_tensors
+    return torch.ops.pylc_hip.multiloss_ignore_backward(dlosses, logits, target, stats, cw, *ctx.w), None, None, None, None, None, None
+
+
+torch.library.register_autograd('pylc_hip::multiloss_ignore', _mli_bwd, setup_context=_mli_setup)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # input normalisation (Model.normalize_image, models/model.py:416-445, + the x3 channel stack :310-311) -> NHWC4 network input
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -446,4 +492,5 @@ def _(img, mean, std):
 
 REGISTERED = ('conv2d', 'conv2d_backward', 'dwconv3x3', 'dwconv3x3_backward', 'batch_norm_act', 'batch_norm_act_backward', 'relu',
               'relu_backward', 'max_pool2d', 'max_pool2d_backward', 'bilinear', 'bilinear_backward', 'global_avg_pool',
-              'global_avg_pool_backward', 'dropout', 'multiloss', 'multiloss_backward', 'image_pack')
+              'global_avg_pool_backward', 'dropout', 'multiloss', 'multiloss_backward', 'multiloss_ignore', 'multiloss_ignore_backward',
+              'image_pack')

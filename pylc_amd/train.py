@@ -37,7 +37,7 @@ def trainer(model, train_batches, valid_batches, n_epochs, save_dir=None, score=
     losses.pth); best_by: 'dice' (the reference's rule) or 'iou' (needs score) picks what the best-model copy follows."""
     if score and model.scores is None:
         from .metrics import ScoreLog
-        model.scores = ScoreLog(model.meta.n_classes)
+        model.scores = ScoreLog(model.meta.n_classes, getattr(model.meta, 'ignore_index', None))
     model.best_by = best_by
     model.net.train()
     offset = model.epoch
