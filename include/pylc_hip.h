@@ -621,6 +621,35 @@ int pylc_image_pack_tiles_ex(const void* img, int is_u8, int Cimg, int H, int W,
                              int n_tiles, const float* mean3, const float* std3, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The streaming mean-probability blend (csrc/blend.hip): pylc_stitch_overlap_argmax's blend taken batch by
+ * batch into one accumulation image, for any network (out = tile is the same-size case), any image size H, W >= out and
+ * any number of ensemble members.  Geometry as above: origins o_i = min(i*stride, n - out), tiles in row-major order.
+ * ------------------------------------------------------------------------------------------- */
+/* logits: the NHWC tiles first_tile .. first_tile+n_tiles-1 of the grid, [n_tiles][out][out][pitch] as a batch of the network
+ * returns them (pitch >= C and a multiple of 4, 16-B aligned).  acc: fp32 [H][W][acc_pitch] (acc_pitch >= C and a multiple
+ * of 4, 16-B aligned), zeroed once by the caller.  For every pixel that a tile of the batch covers,
+ * acc[y][x][c] += softmax(that tile's logits at the pixel)[c], the covering tiles taken in ascending tile index; other pixels
+ * are not written.  flip = 1: the tile holds the logits of the horizontally mirrored window (local column lx is read at
+ * out-1-lx).  After batches that walk all tiles in ascending order acc holds, bit for bit, the sums
+ * pylc_stitch_overlap_argmax forms: the result does not depend on the batch size.  C in 2..16. */
+int pylc_blend_accumulate(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
+                          int flip, float* acc, int acc_pitch, void* stream);
+/* p[c] = acc[y][x][c] / (float)(members * number of tiles covering the pixel), the count taken from the geometry;
+ * mask[H][W] (uint8, 4-B aligned) = first maximum; probs: NULL or fp32 [C][H][W]; conf: NULL or fp32 [H][W], the maximum's
+ * value (the same float as probs[mask]). */
+int pylc_blend_finalize(const float* acc, int acc_pitch, int H, int W, int out, int stride, int C, int members,
+                        unsigned char* mask, float* probs, float* conf, void* stream);
+/* pylc_image_pack_tiles_ex with a trailing flip: flip = 1 writes every window mirrored along x (output column c0 reads source
+ * column x0 + tile - 1 - c0); flip = 0 gives pylc_image_pack_tiles_ex's bytes. */
+int pylc_image_pack_tiles_flip(const void* img, int is_u8, int Cimg, int H, int W, int tile, int stride, int first_tile,
+                               int n_tiles, const float* mean3, const float* std3, float* out, void* stream, int flip);
+/* pylc_image_pack_tiles_reflect with the same trailing flip, and with tile == out (pad = 0) accepted: a same-size network on
+ * the any-size grid. */
+int pylc_image_pack_tiles_reflect_ex(const void* img, int is_u8, int Cimg, int H, int W, int tile, int out, int stride,
+                                     int first_tile, int n_tiles, const float* mean3, const float* std3, float* tiles,
+                                     void* stream, int flip);
+
+/* ---------------------------------------------------------------------------------------------
  * Training tile sets (csrc/dataset.hip): the reference's `pylc.py extract` (Extractor.extract -> __split,
  * utils/extract.py:106-231, 279-310) and the sums its dataset profile is made of (utils/profile.py:92-150).
  * Integer arithmetic only: the results are exact and independent of band_rows and of first_tile chunking.

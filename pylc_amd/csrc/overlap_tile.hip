@@ -16,40 +16,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "overlap_geom.h"      // the geometry: overlap_count, overlap_origin, overlap_cover, reflect101, overlap_check
 
 namespace pylc {
 
 namespace {
 
-typedef float ot_f32x4 __attribute__((ext_vector_type(4)));
-
 struct OverlapGeom { int H, W, out, stride, rows, cols, pitch; };
-
-// number of output-tile origins along an axis of length n (n >= out)
-__host__ __device__ inline int overlap_count(int n, int out, int stride) { return (n - out + stride - 1) / stride + 1; }
-
-// origin of tile i along an axis of length n
-__device__ __forceinline__ int overlap_origin(int i, int n, int out, int stride) {
-    const int o = i * stride;
-    return o < n - out ? o : n - out;
-}
-
-// tiles covering coordinate y along an axis: the unclamped tiles lo .. hi (origin i*stride), then the clamped last tile cnt-1 when
-// y >= n - out.  Visited as a = lo .. hi + last, tile = a <= hi ? a : cnt - 1 (ascending either way; lo <= hi + 1 always).
-struct Cover { int lo, hi, last; };
-__device__ __forceinline__ Cover overlap_cover(int y, int n, int out, int stride, int cnt) {
-    Cover c;
-    c.lo = y < out ? 0 : (y - out) / stride + 1;
-    const int h = y / stride;
-    c.hi = h < cnt - 2 ? h : cnt - 2;
-    c.last = y >= n - out ? 1 : 0;
-    return c;
-}
-
-__device__ __forceinline__ int reflect101(int y, int n) {
-    y = y < 0 ? -y : y;
-    return y >= n ? 2 * (n - 1) - y : y;
-}
 
 // tiles [count][tile][tile][4] <- normalised mirrored windows of img [Cimg][H][W] (raw 0..255), tiles first .. first+count-1 in
 // row-major tile order.  pack_tiles_kernel's arithmetic, ((v - m) / s) / 255, channel 3 = 0; one channel is copied into three.
@@ -81,8 +54,6 @@ __global__ __launch_bounds__(256) void pack_tiles_reflect_kernel(const void* __r
         *reinterpret_cast<ot_f32x4*>(tiles + 4 * i) = v;
     }
 }
-
-constexpr int kOtPx = 4;      // consecutive pixels per lane: the mask leaves as one dword per lane
 
 // logits [rows*cols][out][out][pitch] (NHWC tiles, row-major tile order) -> mask [H][W] (uint8), probs [C][H][W] (fp32, optional).
 // Lane q owns the linear pixels 4q .. 4q+3 (they may straddle a row or a tile edge: every pixel finds its own covering tiles); the
@@ -154,20 +125,6 @@ __global__ __launch_bounds__(256) void stitch_overlap_kernel(const float* __rest
             for (int p = 0; p < np; ++p) mask[base + p] = (unsigned char)(packed >> (8 * p));
         }
     }
-}
-
-inline int ot_grid(long long n) {
-    const long long b = cdiv<long long>(n, 256);
-    return (int)(b < 8192 ? (b < 1 ? 1 : b) : 8192);
-}
-
-// the geometry both entry points accept (pylc_amd/inference.py:overlap_tile_grid raises on the same conditions)
-inline int overlap_check(const char* who, int H, int W, int out, int stride, int pad) {
-    PYLC_REQUIRE(out > 0 && pad >= 0, "%s: out=%d pad=%d", who, out, pad);
-    PYLC_REQUIRE(stride >= 1 && stride <= out, "%s: stride %d outside [1, out=%d]", who, stride, out);
-    PYLC_REQUIRE(H >= out && W >= out, "%s: image %dx%d smaller than the output tile %d", who, H, W, out);
-    PYLC_REQUIRE(pad < H && pad < W, "%s: pad %d must be below the image size %dx%d (one reflection)", who, pad, H, W);
-    return PYLC_OK;
 }
 
 }  // namespace

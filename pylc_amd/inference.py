@@ -57,7 +57,8 @@ def tile_grid(h, w, tile, stride):
     return (h - tile) // stride + 1, (w - tile) // stride + 1
 
 
-def predict_image(model, image, tile=512, stride=None, batch=8, group=None):
+def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blend='reference', flip=False, return_probs=False,
+                  return_confidence=False):
     """image: [C,H,W] raw 0..255 float tensor (host or device), fitted.  Returns the uint8 class mask [H,W] (device).
 
     group=None (default): LOCAL -- this process runs every tile and returns the mask, also inside a data-parallel job (a rank-0-only
@@ -65,9 +66,24 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None):
     group must make: the tile batches are dealt round-robin over the ranks -- every rank holds the image and a replica of the model --
     and the logit tiles are gathered to rank 0, which stitches; the other ranks return None.
 
-    A U-Net model (meta.arch == 'unet') takes predict_overlap_tile instead (any image size, stride default tile - 2*pad)."""
+    blend='reference' (default) is the reference's reconstruct() with its quirks (csrc/stitch.hip); it has no probabilities, so flip,
+    return_probs and return_confidence raise ValueError with it.  blend='mean' is the streaming mean-probability blend
+    (predict_blend_mean, csrc/blend.hip): image uint8 or float, any H, W >= tile, any stride in [1, tile] (default tile // 2); returns the
+    mask, or the tuple (mask[, probs][, conf]) in that order -- probs fp32 [n_classes,H,W], conf fp32 [H,W] its maximum over the classes.
+    flip=True adds the horizontally mirrored windows as a second ensemble member.
+
+    A U-Net model (meta.arch == 'unet') takes predict_overlap_tile instead (any image size, stride default tile - 2*pad); its blend
+    always was the mean, so `blend` is ignored and the other keywords pass through."""
+    if blend not in ('reference', 'mean'):
+        raise ValueError("blend is 'reference' or 'mean', got %r" % (blend,))
     if model.meta.arch == 'unet':
-        return predict_overlap_tile(model, image, tile, stride, batch, group)
+        return predict_overlap_tile(model, image, tile, stride, batch, group, return_probs, flip, return_confidence)
+    if blend == 'mean':
+        return predict_blend_mean(model, image, tile, tile, stride, batch, group, flip, return_probs, return_confidence)
+    asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence)) if v]
+    if asked:
+        raise ValueError("%s needs blend='mean': the reference stitch mixes logits and probabilities, its scores are not probabilities"
+                         % ', '.join(asked))
     L.init()
     stride = tile // 2 if stride is None else stride          # test.py:63
     dev = model.device
@@ -153,7 +169,7 @@ def overlap_tile_out(net, tile, pad):
     return out
 
 
-def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=None, return_probs=False):
+def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=None, return_probs=False, flip=False, return_confidence=False):
     """Full-image U-Net inference by overlap tiles.  image: [C,H,W] raw 0..255, uint8 or float, host or device, any H, W >= out
     (out = tile - 2*meta.pad_size; no fitting).  stride in [1, out], default out.  Returns the uint8 class mask [H,W] (device), or
     (mask, probs) with probs the fp32 mean softmax probabilities [n_classes,H,W] when return_probs.
@@ -161,12 +177,17 @@ def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=Non
     The mirrored windows are cut and normalised on the device (predict_image's statistics), run through model.net in eval mode in
     batches of `batch`, and every logit tile stays in HBM until one kernel blends them: each pixel's class scores are the mean of the
     softmax probabilities of the tiles covering it, its class their argmax.  `group`: predict_image's contract (batches dealt over the
-    ranks, logit tiles gathered to rank 0, which stitches and returns; the other ranks return None)."""
-    L.init()
+    ranks, logit tiles gathered to rank 0, which stitches and returns; the other ranks return None).
+
+    flip=True (the mirrored windows as a second ensemble member) or return_confidence=True (the tuple grows by conf, fp32 [H,W], the
+    maximum probability) move the call to the streaming accumulator, predict_blend_mean; without them it is the one-launch stitch."""
     if model.meta.arch != 'unet':
         raise ValueError('predict_overlap_tile needs a U-Net (meta.arch == "unet"), got %r' % model.meta.arch)
+    L.init()
     pad = model.meta.pad_size
     out = overlap_tile_out(model.net, tile, pad)
+    if flip or return_confidence:
+        return predict_blend_mean(model, image, tile, out, stride, batch, group, flip, return_probs, return_confidence)
     stride = out if stride is None else int(stride)
     dev = model.device
     u8 = image.dtype == torch.uint8            # a photograph: a quarter of the bytes to upload, normalised straight from them
@@ -206,6 +227,81 @@ def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=Non
         if logits is None:
             return None
     return _stitch_overlap(logits, cp, n, h, w, out, stride, ncls, return_probs)
+
+
+def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None, flip=False, return_probs=False, return_confidence=False):
+    """The streaming mean-probability blend (csrc/blend.hip) for a network that maps a `tile` window to its centred `out`
+    square (DeepLab: out = tile; U-Net: out = tile - 2*pad).  image: [C,H,W] raw 0..255, uint8 or float, any H, W >= out; stride in
+    [1, out], default tile // 2 for a same-size network and out otherwise.
+
+    Windows are cut by pylc_image_pack_tiles_reflect_ex, each batch's logits go straight from the network's output (at its own pitch) into
+    pylc_blend_accumulate, which adds their softmax probabilities into one fp32 image [H,W,cp]; pylc_blend_finalize divides by the number
+    of covering tiles and members once at the end.  No logit tile outlives its batch.  flip=True runs a second sweep, member-major: all
+    tiles unflipped, then all tiles cut and accumulated mirrored.  The tiles are visited in ascending index within and across batches, so
+    the result does not depend on `batch`.
+
+    `group`: every rank accumulates its share of the batches into its own image, dist.all_reduce sums them (results then differ from one
+    process's by fp32 summation order only; a one-rank group equals no group bit for bit), rank 0 finalizes, the others return None.
+    Returns mask, or (mask[, probs][, conf])."""
+    L.init()
+    if stride is None:
+        stride = tile // 2 if out == tile else out
+    stride = int(stride)
+    dev = model.device
+    u8 = image.dtype == torch.uint8
+    img = image.to(dev, dtype=torch.uint8 if u8 else torch.float32).contiguous()
+    cimg, h, w = img.shape
+    if cimg != model.meta.ch:
+        raise ValueError('model expects %d-channel images' % model.meta.ch)
+    row_o, col_o = overlap_tile_grid(h, w, out, stride, (tile - out) // 2)
+    n = len(row_o) * len(col_o)
+    mean, std, denom = model._stats(model.meta.normalize_default)
+    if denom != 255.0:                  # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
+        std = [v * denom / 255.0 for v in std]
+    world = dist.get_world_size(group) if group is not None else 1
+    rank = dist.get_rank(group) if group is not None else 0
+    mine = shard_batches(n, batch, rank, world)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    ncls = model.meta.n_classes
+    cp = (ncls + 3) & ~3
+    acc = torch.zeros((h, w, cp), device=dev)
+    members = 2 if flip else 1
+    was_training = model.net.training
+    model.net.eval()
+    try:
+        model._refresh_for_inference()
+        with torch.no_grad():
+            for member in range(members):                   # member-major: the sums of member 0 are complete before member 1 adds to them
+                for k, b in mine:
+                    x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
+                    check(lib.pylc_image_pack_tiles_reflect_ex(ptr(img), int(u8), cimg, h, w, tile, out, stride, k, b, m, s, ptr(x4), stream(),
+                                                               member))
+                    y = ops.as_nhwc(model.net(x4))                     # [b, ncls, out, out], NHWC memory
+                    if tuple(y.shape[1:]) != (ncls, out, out):
+                        raise ValueError('the network returned %s for %d px windows, not %d classes of %d px' % (tuple(y.shape), tile, ncls, out))
+                    p = ops.pitch_of(y)
+                    if p % 4 or y.data_ptr() % 16:                      # a pitch the 16-byte loads cannot take: one relayout to pitch cp
+                        y2 = ops.zeros_nhwc(b, ncls, out, out, dev, pitch=cp)
+                        y2.copy_(y)
+                        y, p = y2, cp
+                    check(lib.pylc_blend_accumulate(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream()))
+    finally:
+        model.net.train(was_training)
+    if world > 1:
+        dist.all_reduce(acc, group=group)
+        if rank != 0:
+            return None
+    return _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence)
+
+
+def _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence):
+    mask = torch.empty((h, w), device=acc.device, dtype=torch.uint8)
+    probs = torch.empty((ncls, h, w), device=acc.device) if return_probs else None
+    conf = torch.empty((h, w), device=acc.device) if return_confidence else None
+    check(lib.pylc_blend_finalize(ptr(acc), cp, h, w, out, stride, ncls, members, ptr(mask), ptr(probs), ptr(conf), stream()))
+    res = (mask,) + ((probs,) if return_probs else ()) + ((conf,) if return_confidence else ())
+    return res if len(res) > 1 else mask
 
 
 def _stitch_overlap(buf, cp, n, h, w, out, stride, ncls, return_probs):

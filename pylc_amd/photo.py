@@ -16,7 +16,9 @@ window on the fitted uint8 image plus pylc_colourize_resize, and step 4 is pylc_
 the image file is the caller's (PIL, imageio or cv2).
 
 A U-Net takes only the scale step and then predict_overlap_tile, which accepts any size: no fit and no resize back.  The reference has
-nothing to match there -- it cannot run a U-Net on a photograph at all (reconstruct() assumes same-size tiles)."""
+nothing to match there -- it cannot run a U-Net on a photograph at all (reconstruct() assumes same-size tiles).  A DeepLab asked for
+blend='mean' takes the same route through the streaming mean-probability blend (inference.predict_blend_mean), which
+is what gives it probabilities, a confidence map and a flip ensemble."""
 import ctypes as C
 import math
 
@@ -25,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from . import metrics, ops, lib as L
-from .inference import gather_tiles, predict_overlap_tile, shard_batches, tile_grid
+from .inference import gather_tiles, predict_blend_mean, predict_overlap_tile, shard_batches, tile_grid
 from .lib import lib, check, ptr, stream
 
 MAX_CLASSES = 16            # PYLC_MAX_CLASSES (include/pylc_hip.h)
@@ -202,39 +204,50 @@ def _predict_fitted(model, img, tile, stride, batch, group):
 
 class PhotoResult:
     """segment_photo's output.  mask: device uint8 [h_scaled, w_scaled] class indices; rgb: device uint8 [h_scaled, w_scaled, 3] when a
-    palette was given (else None); geometry: fit_geometry's dict; probs: the U-Net's mean softmax probabilities [n_classes, h_scaled,
-    w_scaled] when asked (else None).  tile and scale are what the ground truth's size is checked with (PhotoEvaluator.add)."""
+    palette was given (else None); geometry: fit_geometry's dict; probs: the mean softmax probabilities [n_classes, h_scaled, w_scaled]
+    when asked (else None); confidence: their maximum over the classes, fp32 [h_scaled, w_scaled], when asked (else None).  tile and
+    scale are what the ground truth's size is checked with (PhotoEvaluator.add)."""
 
-    def __init__(self, mask, rgb, geometry, probs, tile, scale):
+    def __init__(self, mask, rgb, geometry, probs, tile, scale, confidence=None):
         self.mask, self.rgb, self.geometry, self.probs, self.tile, self.scale = mask, rgb, geometry, probs, tile, scale
+        self.confidence = confidence
 
 
-def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None, batch=8, group=None, return_probs=False):
+def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None, batch=8, group=None, return_probs=False, blend='reference',
+                  flip=False, return_confidence=False):
     """A decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1] grayscale uint8, numpy or tensor) -> PhotoResult at the scaled size.
 
-    DeepLab: fit (stride default tile // 2, test.py:63), predict_image's sliding window on the uint8 fitted image, pylc_colourize_resize
-    back to (h_scaled, w_scaled), then pylc_class_encode_resize of that colour image: the reference's round trip (colourize, resize,
-    class_encode), repeated palette colours included.  Without a palette the identity palette (k, k, k) gives the nearest-resized mask.
+    DeepLab, blend='reference' (default): fit (stride default tile // 2, test.py:63), predict_image's sliding window on the uint8 fitted
+    image, pylc_colourize_resize back to (h_scaled, w_scaled), then pylc_class_encode_resize of that colour image: the reference's round
+    trip (colourize, resize, class_encode), repeated palette colours included.  Without a palette the identity palette (k, k, k) gives the
+    nearest-resized mask.  The reference stitch has no probabilities: flip, return_probs and return_confidence need blend='mean'.
 
-    U-Net: the scale step only, then predict_overlap_tile at the scaled size (stride default its output tile); no fit, no resize back.
+    U-Net, and DeepLab with blend='mean': the scale step only, then the mean-probability blend at the scaled size (predict_overlap_tile,
+    stride default its output tile; for DeepLab predict_image(blend='mean'), stride default tile // 2); no fit, no resize back.
+    return_probs / return_confidence fill PhotoResult.probs / .confidence; flip=True adds the mirrored windows as a second member.
 
     The model's channel count must match the image's; the network runs in eval mode and gets its mode back.  `group`: predict_image's
     contract -- every rank fits its own copy and runs its share of the tile batches, rank 0 stitches, resizes and returns, the others
     return None."""
-    L.init()
     shape = tuple(image.shape)
     ch = 1 if len(shape) == 2 else shape[2]
     if ch != model.meta.ch:
         raise ValueError('model expects %d-channel images, the photograph has %d' % (model.meta.ch, ch))
-    dev = model.device
+    if blend not in ('reference', 'mean'):
+        raise ValueError("blend is 'reference' or 'mean', got %r" % (blend,))
     unet = model.meta.arch == 'unet'
-    if return_probs and not unet:
-        raise ValueError('return_probs: only the U-Net blend has probabilities (the sliding-window stitch mixes logits and probabilities)')
+    if not unet and blend == 'reference':
+        asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence)) if v]
+        if asked:
+            raise ValueError("%s needs blend='mean' on a DeepLab: the reference sliding-window stitch mixes logits and probabilities, its "
+                             "scores are not probabilities" % ', '.join(asked))
+    L.init()
+    dev = model.device
     pal = _palette_tensor(palette, model.meta.n_classes, dev) if palette is not None else None
     was_training = model.net.training
     model.net.eval()
     try:
-        if unet:
+        if unet or blend == 'mean':
             h_s, w_s = scaled_size(shape[0], shape[1], tile, scale)
             if h_s > shape[0] or w_s > shape[1] or h_s == 0 or w_s == 0:
                 raise ValueError('photograph %dx%d (HxW) at scale %s gives %dx%d: INTER_AREA downscales only here' % (shape[0], shape[1], scale,
@@ -242,15 +255,21 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
             geom = {'w_full': shape[1], 'h_full': shape[0], 'w_scaled': w_s, 'h_scaled': h_s, 'w_fitted': w_s, 'h_fitted': h_s,
                     'offset': 0}                      # Extractor.extract(fit=False): (img, w_scaled, h_scaled, 0)
             img = resize_area(_upload_photo(image, dev), h_s, w_s)      # at its own size: a relayout to [C,H,W]
-            got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs)
+            if unet:
+                got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence)
+            else:
+                got = predict_blend_mean(model, img, tile, tile, stride, batch, group, flip, return_probs, return_confidence)
             if got is None:
                 return None
-            mask, probs = got if return_probs else (got, None)
+            got = list(got) if isinstance(got, tuple) else [got]
+            mask = got.pop(0)
+            probs = got.pop(0) if return_probs else None
+            conf = got.pop(0) if return_confidence else None
             rgb = None
             if pal is not None:
                 rgb = _colourize(mask, pal, h_s, w_s)
                 mask = _encode(rgb, pal)
-            return PhotoResult(mask, rgb, geom, probs, tile, scale)
+            return PhotoResult(mask, rgb, geom, probs, tile, scale, conf)
         stride = tile // 2 if stride is None else stride          # test.py:63
         img, geom = fit_image(image, tile, stride, scale, dev)
         fitted = _predict_fitted(model, img, tile, stride, batch, group)
