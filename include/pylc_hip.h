@@ -712,6 +712,33 @@ int pylc_logits_score(const float* logits, int pitch, const void* target, int ta
 int pylc_logits_score_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
                          int ignore_index, unsigned long long* counts, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Connected regions of a class mask and the small-region sieve (csrc/regions.hip; not in the reference).
+ * mask: uint8 [H][W], any values, contiguous, any byte address, 1 <= H*W < 2^31.  A region is a maximal set of pixels of one
+ * value connected through 4-neighbours (connectivity 4) or 8-neighbours (8); pixels equal to ignore_index (0..255, or -1
+ * for none) belong to no region.  Everything is integer and canonical: no result depends on the order in which blocks run.
+ * ------------------------------------------------------------------------------------------- */
+/* labels: int32 [H][W] (4-B aligned): the linear index y*W + x of the first pixel of the pixel's region in raster order
+ * (the region's minimum index, its "root"), -1 at ignored pixels.  Three launches (tile, border, flatten); needs no workspace.
+ * A NULL pointer, connectivity other than 4 / 8, H or W < 1, H*W >= 2^31, ignore_index outside -1..255: PYLC_ERR_ARG,
+ * nothing is launched. */
+int pylc_label_regions(const unsigned char* mask, int H, int W, int connectivity, int ignore_index, int* labels, void* stream);
+/* sizes: int32 [N], written in full: sizes[r] = number of pixels whose label is r (so the region's pixel count at its root
+ * and 0 at every other index); labels < 0 are not counted.  labels are pylc_label_regions' (values -1..N-1).
+ * A NULL pointer, N < 1 or N >= 2^31: PYLC_ERR_ARG, nothing is launched. */
+int pylc_region_sizes(const int* labels, long long N, int* sizes, void* stream);
+/* One sieve pass: out[H][W] = mask with every pixel of a SMALL region (size < min_size) replaced.  fill 0..255: by that value.
+ * fill -1, the neighbour rule: by the value of the region's largest LARGE neighbour -- a region of size >= min_size sharing a
+ * 4-neighbour pixel pair with it (for both connectivities); equal sizes go to the smaller root, i.e. the maximum of
+ * key = size << 32 | (0xFFFFFFFF - root) wins; a small region without a large neighbour keeps its value.  Ignored pixels
+ * (labels < 0) are copied and lend no value.  labels / sizes: the two entry points' above for the same mask.  best_ws: device
+ * workspace of H*W x 8 bytes (8-B aligned), zeroed here; not touched with a constant fill (may then be NULL).  out may not
+ * alias mask.  n_changed: NULL, or a device int64 into which the number of pixels with out != mask is ADDED.  ignore_index
+ * is checked for its range only: the labels already say which pixels are ignored.  A NULL pointer, H*W out of range,
+ * min_size < 1, fill or ignore_index outside -1..255, out == mask: PYLC_ERR_ARG, nothing is launched. */
+int pylc_sieve_regions(const unsigned char* mask, const int* labels, const int* sizes, int H, int W, int min_size, int ignore_index,
+                       int fill, unsigned long long* best_ws, unsigned char* out, long long* n_changed, void* stream);
+
 /* The general form: ((x - mean[c]) / std[c]) / denom on float (is_u8 = 0) or uint8 (is_u8 = 1) tiles.  denom = 255 is
  * pylc_image_pack[_u8]; denom = 1 is the reference's grayscale `default=True` branch, which omits the division by 255
  * (models/model.py:428-430). */

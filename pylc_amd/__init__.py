@@ -9,3 +9,4 @@ from . import lib  # noqa: F401  (raises if libpylc_hip.so is missing)
 from .runtime import runtime  # noqa: F401
 from .nets import DeepLab, UNet  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.pylc_hip.*)
+from . import regions  # noqa: F401  (connected regions and the small-region sieve of class masks)

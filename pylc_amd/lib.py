@@ -200,6 +200,9 @@ SIGNATURES = {
     'pylc_confusion_matrix_ex': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _I, _P, _P]),
     'pylc_logits_score': (_I, [_P, _I, _P, _I, _LL, _I, _P, _P, _P]),
     'pylc_logits_score_ex': (_I, [_P, _I, _P, _I, _LL, _I, _P, _I, _P, _P]),
+    'pylc_label_regions': (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    'pylc_region_sizes': (_I, [_P, _LL, _P, _P]),
+    'pylc_sieve_regions': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     'pylc_nhwc_to_nchw': (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     'pylc_nchw_to_nhwc': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'pylc_multiloss_workspace_floats': (_SZ, [_LL, _I]),

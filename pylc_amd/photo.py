@@ -26,7 +26,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import metrics, ops, lib as L
+from . import metrics, ops, regions, lib as L
 from .inference import gather_tiles, predict_blend_mean, predict_overlap_tile, shard_batches, tile_grid
 from .lib import lib, check, ptr, stream
 
@@ -206,15 +206,29 @@ class PhotoResult:
     """segment_photo's output.  mask: device uint8 [h_scaled, w_scaled] class indices; rgb: device uint8 [h_scaled, w_scaled, 3] when a
     palette was given (else None); geometry: fit_geometry's dict; probs: the mean softmax probabilities [n_classes, h_scaled, w_scaled]
     when asked (else None); confidence: their maximum over the classes, fp32 [h_scaled, w_scaled], when asked (else None).  tile and
-    scale are what the ground truth's size is checked with (PhotoEvaluator.add)."""
+    scale are what the ground truth's size is checked with (PhotoEvaluator.add).  n_sieved: with min_region, a device int64 scalar, the
+    number of mask pixels the sieve replaced (else None)."""
 
-    def __init__(self, mask, rgb, geometry, probs, tile, scale, confidence=None):
+    def __init__(self, mask, rgb, geometry, probs, tile, scale, confidence=None, n_sieved=None):
         self.mask, self.rgb, self.geometry, self.probs, self.tile, self.scale = mask, rgb, geometry, probs, tile, scale
         self.confidence = confidence
+        self.n_sieved = n_sieved
+
+
+def _sieve_result(res, pal, min_region, connectivity, fill, ignore_index):
+    """The small-region sieve (regions.sieve) as segment_photo's last step: on the scaled-size mask, the colour image
+    recoloured from the sieved mask; probs and confidence stay what the network said."""
+    res.mask, res.n_sieved = regions.sieve(res.mask, min_region, connectivity, fill, ignore_index, return_changed=True)
+    if res.rgb is not None:
+        # a constant fill may lie outside the palette (fill='ignore'): colour through 256 entries, black past the palette's own
+        pal256 = torch.zeros((256, 3), device=pal.device, dtype=torch.uint8)
+        pal256[:pal.shape[0]] = pal
+        res.rgb = _colourize(res.mask, pal256, res.mask.shape[0], res.mask.shape[1])
+    return res
 
 
 def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None, batch=8, group=None, return_probs=False, blend='reference',
-                  flip=False, return_confidence=False):
+                  flip=False, return_confidence=False, min_region=0, region_connectivity=4, region_fill='neighbour', ignore_index=None):
     """A decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1] grayscale uint8, numpy or tensor) -> PhotoResult at the scaled size.
 
     DeepLab, blend='reference' (default): fit (stride default tile // 2, test.py:63), predict_image's sliding window on the uint8 fitted
@@ -225,6 +239,11 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     U-Net, and DeepLab with blend='mean': the scale step only, then the mean-probability blend at the scaled size (predict_overlap_tile,
     stride default its output tile; for DeepLab predict_image(blend='mean'), stride default tile // 2); no fit, no resize back.
     return_probs / return_confidence fill PhotoResult.probs / .confidence; flip=True adds the mirrored windows as a second member.
+
+    min_region > 1: regions of the final mask below that many pixels are sieved (regions.sieve with region_connectivity, region_fill and
+    ignore_index; one pass), PhotoResult.rgb is recoloured from the sieved mask and PhotoResult.n_sieved counts the replaced pixels.  A
+    region_fill of 'ignore' (or of ignore_index itself) leaves unlabelled pixels, which a palette has no colour for: rgb is black (0, 0, 0)
+    there.  0 (default): the path without it, launch for launch.
 
     The model's channel count must match the image's; the network runs in eval mode and gets its mode back.  `group`: predict_image's
     contract -- every rank fits its own copy and runs its share of the tile batches, rank 0 stitches, resizes and returns, the others
@@ -241,6 +260,10 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
         if asked:
             raise ValueError("%s needs blend='mean' on a DeepLab: the reference sliding-window stitch mixes logits and probabilities, its "
                              "scores are not probabilities" % ', '.join(asked))
+    sieving = int(min_region) > 1
+    if sieving:                                      # argument errors before any launch
+        regions._check_mask(torch.empty((1, 1), dtype=torch.uint8), region_connectivity, ignore_index)
+        regions._fill_value(region_fill, ignore_index)
     L.init()
     dev = model.device
     pal = _palette_tensor(palette, model.meta.n_classes, dev) if palette is not None else None
@@ -269,7 +292,8 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
             if pal is not None:
                 rgb = _colourize(mask, pal, h_s, w_s)
                 mask = _encode(rgb, pal)
-            return PhotoResult(mask, rgb, geom, probs, tile, scale, conf)
+            res = PhotoResult(mask, rgb, geom, probs, tile, scale, conf)
+            return _sieve_result(res, pal, int(min_region), region_connectivity, region_fill, ignore_index) if sieving else res
         stride = tile // 2 if stride is None else stride          # test.py:63
         img, geom = fit_image(image, tile, stride, scale, dev)
         fitted = _predict_fitted(model, img, tile, stride, batch, group)
@@ -281,7 +305,8 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     enc = pal if pal is not None else torch.arange(model.meta.n_classes, device=dev, dtype=torch.uint8)[:, None].expand(-1, 3).contiguous()
     rgb = _colourize(fitted, enc, h_s, w_s)
     mask = _encode(rgb, enc)
-    return PhotoResult(mask, rgb if pal is not None else None, geom, None, tile, scale)
+    res = PhotoResult(mask, rgb if pal is not None else None, geom, None, tile, scale)
+    return _sieve_result(res, pal, int(min_region), region_connectivity, region_fill, ignore_index) if sieving else res
 
 
 # ---- scores ----------------------------------------------------------------------------------------------------------------------
