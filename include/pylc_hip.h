@@ -650,6 +650,33 @@ int pylc_image_pack_tiles_reflect_ex(const void* img, int is_u8, int Cimg, int H
                                      void* stream, int flip);
 
 /* ---------------------------------------------------------------------------------------------
+ * The multi-scale ensemble on the streaming blend (csrc/multiscale.hip; the published DeepLabV3+ multi-scale
+ * protocol, not in the reference): the photograph run at several sizes, each size's mean probabilities resampled to the
+ * photograph's size, their weighted mean.  One coordinate rule, per axis with destination length n and source length ns:
+ * s = (i + 0.5) * ((double)ns / n) - 0.5 in double, clamped to [0, ns - 1]; i0 = floor(s), i1 = min(i0 + 1, ns - 1),
+ * f = (float)(s - i0); value = (1-fy)*((1-fx)*v00 + fx*v01) + fy*((1-fx)*v10 + fx*v11) in fp32, in that order (half-pixel
+ * centres: torch's F.interpolate(mode='bilinear', align_corners=False) without antialiasing).  ns == n gives v00 bit for bit,
+ * through the same code.  The three entry points check their arguments on the host (PYLC_ERR_ARG, nothing is launched),
+ * allocate nothing and enqueue on `stream`.
+ * ------------------------------------------------------------------------------------------- */
+/* src: planar [Cimg][H][W], uint8 (is_u8 = 1) or float32 (is_u8 = 0), Cimg 1 or 3; dst: planar float32 [Cimg][oh][ow], the
+ * layout the tile cutters read with is_u8 = 0.  Any ratio, H, W, oh, ow >= 1; no area prefilter: a downscale below 1/2 skips
+ * source pixels. */
+int pylc_resize_bilinear_image(const void* src, int is_u8, int Cimg, int H, int W, float* dst, int oh, int ow, void* stream);
+/* acc_s: a finished accumulation image of pylc_blend_accumulate at the scaled size, fp32 [Hs][Ws][src_pitch], with the geometry
+ * (out, stride) and the number of members it was summed over.  At a source pixel p[c] = acc_s[..][c] / (float)(members * number
+ * of tiles covering it), pylc_blend_finalize's division.  ens: fp32 [H][W][ens_pitch]; for every pixel and c < C
+ * ens[y][x][c] = (add ? ens[y][x][c] : 0) + weight * bilinear(p)[c].  add = 0 does not read ens; channels C .. ens_pitch-1 are
+ * never written.  Pitches >= C and multiples of 4, both images 16-B aligned and distinct; Hs, Ws >= out, 1 <= stride <= out,
+ * members >= 1, weight > 0 and finite, H, W >= 1, C in 2..16. */
+int pylc_blend_resample_accumulate(const float* acc_s, int src_pitch, int Hs, int Ws, int out, int stride, int members, float weight,
+                                   int C, float* ens, int ens_pitch, int H, int W, int add, void* stream);
+/* p[c] = ens[y][x][c] / total_weight (> 0, finite); mask, probs and conf exactly as pylc_blend_finalize writes them (the same
+ * kernel body with one divisor for every pixel). */
+int pylc_ensemble_finalize(const float* ens, int pitch, int H, int W, int C, float total_weight, unsigned char* mask, float* probs,
+                           float* conf, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training tile sets (csrc/dataset.hip): the reference's `pylc.py extract` (Extractor.extract -> __split,
  * utils/extract.py:106-231, 279-310) and the sums its dataset profile is made of (utils/profile.py:92-150).
  * Integer arithmetic only: the results are exact and independent of band_rows and of first_tile chunking.

@@ -7,8 +7,9 @@
 //                               pixel's acc vector loaded once, added to in registers and stored once (16-byte accesses, no atomics).
 //                               Tile index ascends within a batch and from batch to batch, so after a member's last batch acc holds,
 //                               bit for bit, the sums stitch_overlap_kernel forms in registers: independent of the batch size.
-//   blend_finalize_kernel<C>    p[c] = acc[c] / (members * covering tiles) -- the count comes from the geometry, no count buffer --
+//   blend_finalize_kernel<C, 1> p[c] = acc[c] / (members * covering tiles) -- the count comes from the geometry, no count buffer --
 //                               class = first maximum; mask (four pixels per lane, one dword), optional probs [C][H][W], conf [H][W].
+//                               (blend_finalize.h: multiscale.hip's ensemble finalizer is the same body with one divisor.)
 //   pack_tiles_flip_kernel      pack_tiles_kernel / pack_tiles_reflect_kernel with an optional mirror along x (column c0 of a window
 //                               reads the window's column tile-1-c0) and pad = 0 allowed.
 //
@@ -16,14 +17,13 @@
 // in which the clamp is never active.  Bandwidth kernels: no LDS, no MFMA.
 #include <type_traits>
 
+#include "blend_finalize.h"
 #include "common.h"
 #include "overlap_geom.h"
 
 namespace pylc {
 
 namespace {
-
-struct BlendGeom { int H, W, out, stride, rows, cols, pitch, acc_pitch; };
 
 // the pixels [y0, y0 + bh) x [x0, x0 + bw) that the tiles first .. first + count - 1 can touch
 struct BlendBox { int y0, x0, bh, bw; };
@@ -84,56 +84,6 @@ __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __re
                 t.x = a[4 * q]; t.y = a[4 * q + 1]; t.z = a[4 * q + 2]; t.w = a[4 * q + 3];
                 dst[q] = t;
             }
-        }
-    }
-}
-
-// acc [H][W][acc_pitch] -> mask [H][W], probs [C][H][W] (optional), conf [H][W] (optional).  Lane q owns the linear pixels 4q .. 4q+3,
-// visited one after the other (stitch_overlap_kernel's rolled loop: an unrolled one spills at C >= 9); the mask leaves as one dword.
-template <int C>
-__global__ __launch_bounds__(256) void blend_finalize_kernel(const float* __restrict__ acc, BlendGeom g, int members,
-                                                              unsigned char* __restrict__ mask, float* __restrict__ probs,
-                                                              float* __restrict__ conf) {
-    constexpr int NV = (C + 3) / 4;
-    const long long total = (long long)g.H * g.W;
-    const long long groups = cdiv<long long>(total, kOtPx);
-    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += (long long)gridDim.x * blockDim.x) {
-        const long long base = q * kOtPx;
-        const int np = total - base < kOtPx ? (int)(total - base) : kOtPx;
-        unsigned int packed = 0;
-#pragma unroll 1
-        for (int p = 0; p < np; ++p) {
-            const long long i = base + p;
-            const int y = (int)(i / g.W), x = (int)(i - (long long)y * g.W);
-            const Cover cy = overlap_cover(y, g.H, g.out, g.stride, g.rows);
-            const Cover cx = overlap_cover(x, g.W, g.out, g.stride, g.cols);
-            const int n = members * (cy.hi + cy.last - cy.lo + 1) * (cx.hi + cx.last - cx.lo + 1);
-            const ot_f32x4* src = reinterpret_cast<const ot_f32x4*>(acc + (size_t)i * g.acc_pitch);
-            float a[NV * 4];
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-                const ot_f32x4 t = src[k];
-                a[4 * k] = t.x; a[4 * k + 1] = t.y; a[4 * k + 2] = t.z; a[4 * k + 3] = t.w;
-            }
-            const float fn = (float)n;
-            int best = 0;
-            float bv = 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                a[c] = a[c] / fn;
-                if (c == 0 || a[c] > bv) { bv = a[c]; best = c; }     // first maximum (np.argmax)
-            }
-            packed |= (unsigned int)best << (8 * p);
-            if (probs != nullptr) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) probs[(size_t)c * total + i] = a[c];
-            }
-            if (conf != nullptr) conf[i] = bv;
-        }
-        if (np == kOtPx) {
-            *reinterpret_cast<unsigned int*>(mask + base) = packed;     // base % 4 == 0: an aligned dword
-        } else {
-            for (int p = 0; p < np; ++p) mask[base + p] = (unsigned char)(packed >> (8 * p));
         }
     }
 }
@@ -216,15 +166,6 @@ extern "C" int pylc_image_pack_tiles_reflect_ex(const void* img, int is_u8, int 
     return launch_pack_flip(img, is_u8, Cimg, H, W, tile, out, stride, cols, first_tile, n_tiles, flip, mean3, std3, tiles, stream);
 }
 
-#define PYLC_BLEND_SWITCH(C, LAUNCH, who)                                                                                              \
-    switch (C) {                                                                                                                       \
-        case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; case 4: LAUNCH(4); break; case 5: LAUNCH(5); break;                        \
-        case 6: LAUNCH(6); break; case 7: LAUNCH(7); break; case 8: LAUNCH(8); break; case 9: LAUNCH(9); break;                        \
-        case 10: LAUNCH(10); break; case 11: LAUNCH(11); break; case 12: LAUNCH(12); break; case 13: LAUNCH(13); break;                \
-        case 14: LAUNCH(14); break; case 15: LAUNCH(15); break; case 16: LAUNCH(16); break;                                            \
-        default: return fail(PYLC_ERR_ARG, who ": n_classes=%d unsupported (2..%d)", C, PYLC_MAX_CLASSES);                             \
-    }
-
 extern "C" int pylc_blend_accumulate(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
                                      int flip, float* acc, int acc_pitch, void* stream) {
     PYLC_REQUIRE(logits && pitch >= C && pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0,
@@ -269,7 +210,7 @@ extern "C" int pylc_blend_finalize(const float* acc, int acc_pitch, int H, int W
     const BlendGeom g{H, W, out, stride, overlap_count(H, out, stride), overlap_count(W, out, stride), 0, acc_pitch};
     const int blocks = ot_grid(cdiv<long long>((long long)H * W, kOtPx));
     hipStream_t st = as_stream(stream);
-#define LAUNCH_BF(CC) hipLaunchKernelGGL((blend_finalize_kernel<CC>), dim3(blocks), dim3(256), 0, st, acc, g, members, mask, probs, conf)
+#define LAUNCH_BF(CC) hipLaunchKernelGGL((blend_finalize_kernel<CC, true>), dim3(blocks), dim3(256), 0, st, acc, g, members, 0.f, mask, probs, conf)
     PYLC_BLEND_SWITCH(C, LAUNCH_BF, "blend_finalize")
 #undef LAUNCH_BF
     PYLC_LAUNCH_CHECK();

@@ -1,0 +1,79 @@
+// The finalizer shared by csrc/blend.hip (pylc_blend_finalize) and csrc/multiscale.hip (pylc_ensemble_finalize): one body, the divisor
+// chosen by a template flag.
+#pragma once
+#include "common.h"
+#include "overlap_geom.h"
+
+namespace pylc {
+
+namespace {
+
+struct BlendGeom { int H, W, out, stride, rows, cols, pitch, acc_pitch; };
+
+// acc [H][W][acc_pitch] -> mask [H][W], probs [C][H][W] (optional), conf [H][W] (optional).  Lane q owns the linear pixels 4q .. 4q+3,
+// visited one after the other (stitch_overlap_kernel's rolled loop: an unrolled one spills at C >= 9); the mask leaves as one dword.
+// kCover: p[c] = acc[c] / (members * covering tiles), the count from the geometry (the blend).  !kCover: p[c] = acc[c] / total, one
+// divisor for every pixel (the ensemble: cover := 1); g.out, g.stride, g.rows, g.cols and members are then not read.
+template <int C, bool kCover>
+__global__ __launch_bounds__(256) void blend_finalize_kernel(const float* __restrict__ acc, BlendGeom g, int members, float total,
+                                                              unsigned char* __restrict__ mask, float* __restrict__ probs,
+                                                              float* __restrict__ conf) {
+    constexpr int NV = (C + 3) / 4;
+    const long long npx = (long long)g.H * g.W;
+    const long long groups = cdiv<long long>(npx, kOtPx);
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += (long long)gridDim.x * blockDim.x) {
+        const long long base = q * kOtPx;
+        const int np = npx - base < kOtPx ? (int)(npx - base) : kOtPx;
+        unsigned int packed = 0;
+#pragma unroll 1
+        for (int p = 0; p < np; ++p) {
+            const long long i = base + p;
+            float fn = total;
+            if constexpr (kCover) {
+                const int y = (int)(i / g.W), x = (int)(i - (long long)y * g.W);
+                const Cover cy = overlap_cover(y, g.H, g.out, g.stride, g.rows);
+                const Cover cx = overlap_cover(x, g.W, g.out, g.stride, g.cols);
+                const int n = members * (cy.hi + cy.last - cy.lo + 1) * (cx.hi + cx.last - cx.lo + 1);
+                fn = (float)n;
+            }
+            const ot_f32x4* src = reinterpret_cast<const ot_f32x4*>(acc + (size_t)i * g.acc_pitch);
+            float a[NV * 4];
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                const ot_f32x4 t = src[k];
+                a[4 * k] = t.x; a[4 * k + 1] = t.y; a[4 * k + 2] = t.z; a[4 * k + 3] = t.w;
+            }
+            int best = 0;
+            float bv = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                a[c] = a[c] / fn;
+                if (c == 0 || a[c] > bv) { bv = a[c]; best = c; }     // first maximum (np.argmax)
+            }
+            packed |= (unsigned int)best << (8 * p);
+            if (probs != nullptr) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) probs[(size_t)c * npx + i] = a[c];
+            }
+            if (conf != nullptr) conf[i] = bv;
+        }
+        if (np == kOtPx) {
+            *reinterpret_cast<unsigned int*>(mask + base) = packed;     // base % 4 == 0: an aligned dword
+        } else {
+            for (int p = 0; p < np; ++p) mask[base + p] = (unsigned char)(packed >> (8 * p));
+        }
+    }
+}
+
+}  // namespace
+
+#define PYLC_BLEND_SWITCH(C, LAUNCH, who)                                                                                              \
+    switch (C) {                                                                                                                       \
+        case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; case 4: LAUNCH(4); break; case 5: LAUNCH(5); break;                        \
+        case 6: LAUNCH(6); break; case 7: LAUNCH(7); break; case 8: LAUNCH(8); break; case 9: LAUNCH(9); break;                        \
+        case 10: LAUNCH(10); break; case 11: LAUNCH(11); break; case 12: LAUNCH(12); break; case 13: LAUNCH(13); break;                \
+        case 14: LAUNCH(14); break; case 15: LAUNCH(15); break; case 16: LAUNCH(16); break;                                            \
+        default: return fail(PYLC_ERR_ARG, who ": n_classes=%d unsupported (2..%d)", C, PYLC_MAX_CLASSES);                             \
+    }
+
+}  // namespace pylc

@@ -58,7 +58,7 @@ def tile_grid(h, w, tile, stride):
 
 
 def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blend='reference', flip=False, return_probs=False,
-                  return_confidence=False):
+                  return_confidence=False, scales=None, scale_weights=None):
     """image: [C,H,W] raw 0..255 float tensor (host or device), fitted.  Returns the uint8 class mask [H,W] (device).
 
     group=None (default): LOCAL -- this process runs every tile and returns the mask, also inside a data-parallel job (a rank-0-only
@@ -70,17 +70,20 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blen
     return_probs and return_confidence raise ValueError with it.  blend='mean' is the streaming mean-probability blend
     (predict_blend_mean, csrc/blend.hip): image uint8 or float, any H, W >= tile, any stride in [1, tile] (default tile // 2); returns the
     mask, or the tuple (mask[, probs][, conf]) in that order -- probs fp32 [n_classes,H,W], conf fp32 [H,W] its maximum over the classes.
-    flip=True adds the horizontally mirrored windows as a second ensemble member.
+    flip=True adds the horizontally mirrored windows as a second ensemble member.  scales=(0.75, 1.0, 1.25) runs the multi-scale ensemble
+    (predict_blend_mean: the image at every scale, the probabilities resampled back and averaged with scale_weights); like flip it needs
+    blend='mean'.
 
     A U-Net model (meta.arch == 'unet') takes predict_overlap_tile instead (any image size, stride default tile - 2*pad); its blend
     always was the mean, so `blend` is ignored and the other keywords pass through."""
     if blend not in ('reference', 'mean'):
         raise ValueError("blend is 'reference' or 'mean', got %r" % (blend,))
     if model.meta.arch == 'unet':
-        return predict_overlap_tile(model, image, tile, stride, batch, group, return_probs, flip, return_confidence)
+        return predict_overlap_tile(model, image, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights)
     if blend == 'mean':
-        return predict_blend_mean(model, image, tile, tile, stride, batch, group, flip, return_probs, return_confidence)
-    asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence)) if v]
+        return predict_blend_mean(model, image, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights)
+    asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence),
+                            ('scales', scales is not None), ('scale_weights', scale_weights is not None)) if v]
     if asked:
         raise ValueError("%s needs blend='mean': the reference stitch mixes logits and probabilities, its scores are not probabilities"
                          % ', '.join(asked))
@@ -169,7 +172,8 @@ def overlap_tile_out(net, tile, pad):
     return out
 
 
-def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=None, return_probs=False, flip=False, return_confidence=False):
+def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=None, return_probs=False, flip=False, return_confidence=False,
+                         scales=None, scale_weights=None):
     """Full-image U-Net inference by overlap tiles.  image: [C,H,W] raw 0..255, uint8 or float, host or device, any H, W >= out
     (out = tile - 2*meta.pad_size; no fitting).  stride in [1, out], default out.  Returns the uint8 class mask [H,W] (device), or
     (mask, probs) with probs the fp32 mean softmax probabilities [n_classes,H,W] when return_probs.
@@ -179,15 +183,16 @@ def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=Non
     softmax probabilities of the tiles covering it, its class their argmax.  `group`: predict_image's contract (batches dealt over the
     ranks, logit tiles gathered to rank 0, which stitches and returns; the other ranks return None).
 
-    flip=True (the mirrored windows as a second ensemble member) or return_confidence=True (the tuple grows by conf, fp32 [H,W], the
-    maximum probability) move the call to the streaming accumulator, predict_blend_mean; without them it is the one-launch stitch."""
+    flip=True (the mirrored windows as a second ensemble member), return_confidence=True (the tuple grows by conf, fp32 [H,W], the
+    maximum probability) or scales (the multi-scale ensemble) move the call to the streaming accumulator, predict_blend_mean; without
+    them it is the one-launch stitch."""
     if model.meta.arch != 'unet':
         raise ValueError('predict_overlap_tile needs a U-Net (meta.arch == "unet"), got %r' % model.meta.arch)
     L.init()
     pad = model.meta.pad_size
     out = overlap_tile_out(model.net, tile, pad)
-    if flip or return_confidence:
-        return predict_blend_mean(model, image, tile, out, stride, batch, group, flip, return_probs, return_confidence)
+    if flip or return_confidence or scales is not None or scale_weights is not None:
+        return predict_blend_mean(model, image, tile, out, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights)
     stride = out if stride is None else int(stride)
     dev = model.device
     u8 = image.dtype == torch.uint8            # a photograph: a quarter of the bytes to upload, normalised straight from them
@@ -229,7 +234,90 @@ def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=Non
     return _stitch_overlap(logits, cp, n, h, w, out, stride, ncls, return_probs)
 
 
-def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None, flip=False, return_probs=False, return_confidence=False):
+SCALE_RANGE = (0.5, 2.0)    # where the plain bilinear resize still reads every source pixel (no area prefilter)
+
+
+def scaled_size(n, s):
+    """The length of an axis of n pixels at scale s, rounded half up: int(n * s + 0.5)."""
+    return int(n * s + 0.5)
+
+
+def resize_image(image, oh, ow):
+    """[C,H,W] raw image, uint8 or float, C 1 or 3 (host or device) -> float32 device [C,oh,ow] by half-pixel-centre bilinear
+    interpolation without antialiasing (pylc_resize_bilinear_image: F.interpolate(mode='bilinear', align_corners=False) with double
+    coordinates), the resize of the published multi-scale protocol.  Any ratio; below 1/2 it skips source pixels."""
+    L.init()
+    dev = image.device if image.is_cuda else torch.device('cuda')
+    u8 = image.dtype == torch.uint8
+    img = image.to(dev, dtype=torch.uint8 if u8 else torch.float32).contiguous()
+    if img.dim() != 3 or img.shape[0] not in (1, 3):
+        raise ValueError('resize_image needs a [C,H,W] image of 1 or 3 channels, got %s' % (tuple(img.shape),))
+    if oh < 1 or ow < 1:
+        raise ValueError('resize_image: output size %dx%d' % (oh, ow))
+    cimg, h, w = img.shape
+    out = torch.empty((cimg, int(oh), int(ow)), device=dev)
+    check(lib.pylc_resize_bilinear_image(ptr(img), int(u8), cimg, h, w, ptr(out), int(oh), int(ow), stream()))
+    return out
+
+
+def ensemble_plan(scales, scale_weights, h, w, out):
+    """The multi-scale ensemble's members for an h x w image and output tile `out`: [(scale, scaled h, scaled w, weight)] in the order
+    given.  ValueError for an empty sequence, a scale outside SCALE_RANGE, weights of another length or not positive, and a scale at
+    which a side falls below the output tile."""
+    scales = [float(s) for s in scales]
+    if not scales:
+        raise ValueError('scales is empty: give at least one scale, or None for the single-scale blend')
+    weights = [1.0] * len(scales) if scale_weights is None else [float(v) for v in scale_weights]
+    if len(weights) != len(scales):
+        raise ValueError('scale_weights has %d entries for %d scales' % (len(weights), len(scales)))
+    plan = []
+    for s, wgt in zip(scales, weights):
+        if not SCALE_RANGE[0] <= s <= SCALE_RANGE[1]:
+            raise ValueError('scale %r outside [%g, %g]: the bilinear resize has no area prefilter' % (s, SCALE_RANGE[0], SCALE_RANGE[1]))
+        if not 0.0 < wgt < float('inf'):
+            raise ValueError('scale weight %r for scale %r is not a positive number' % (wgt, s))
+        hs, ws = scaled_size(h, s), scaled_size(w, s)
+        if hs < out or ws < out:
+            raise ValueError('scale %r takes the %dx%d image to %dx%d, below the output tile %d (need H, W >= out at every scale)'
+                             % (s, h, w, hs, ws, out))
+        plan.append((s, hs, ws, wgt))
+    return plan
+
+
+def _blend_sweep(model, img, tile, out, stride, batch, group, members, norm):
+    """predict_blend_mean's sweep over one device image [C,H,W] (uint8 or float32): this rank's share of the tile batches, member-major,
+    into a zeroed accumulation image [H,W,cp], which it returns.  The network is in eval mode already."""
+    dev = model.device
+    u8 = img.dtype == torch.uint8
+    cimg, h, w = img.shape
+    row_o, col_o = overlap_tile_grid(h, w, out, stride, (tile - out) // 2)
+    n = len(row_o) * len(col_o)
+    world = dist.get_world_size(group) if group is not None else 1
+    rank = dist.get_rank(group) if group is not None else 0
+    mine = shard_batches(n, batch, rank, world)
+    m, s = norm
+    ncls = model.meta.n_classes
+    cp = (ncls + 3) & ~3
+    acc = torch.zeros((h, w, cp), device=dev)
+    for member in range(members):                   # member-major: the sums of member 0 are complete before member 1 adds to them
+        for k, b in mine:
+            x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
+            check(lib.pylc_image_pack_tiles_reflect_ex(ptr(img), int(u8), cimg, h, w, tile, out, stride, k, b, m, s, ptr(x4), stream(),
+                                                       member))
+            y = ops.as_nhwc(model.net(x4))                     # [b, ncls, out, out], NHWC memory
+            if tuple(y.shape[1:]) != (ncls, out, out):
+                raise ValueError('the network returned %s for %d px windows, not %d classes of %d px' % (tuple(y.shape), tile, ncls, out))
+            p = ops.pitch_of(y)
+            if p % 4 or y.data_ptr() % 16:                      # a pitch the 16-byte loads cannot take: one relayout to pitch cp
+                y2 = ops.zeros_nhwc(b, ncls, out, out, dev, pitch=cp)
+                y2.copy_(y)
+                y, p = y2, cp
+            check(lib.pylc_blend_accumulate(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream()))
+    return acc
+
+
+def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None, flip=False, return_probs=False, return_confidence=False,
+                       scales=None, scale_weights=None):
     """The streaming mean-probability blend (csrc/blend.hip) for a network that maps a `tile` window to its centred `out`
     square (DeepLab: out = tile; U-Net: out = tile - 2*pad).  image: [C,H,W] raw 0..255, uint8 or float, any H, W >= out; stride in
     [1, out], default tile // 2 for a same-size network and out otherwise.
@@ -240,66 +328,82 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
     tiles unflipped, then all tiles cut and accumulated mirrored.  The tiles are visited in ascending index within and across batches, so
     the result does not depend on `batch`.
 
+    scales (csrc/multiscale.hip): None is the single-scale blend above.  A sequence of floats in [0.5, 2.0] runs the
+    multi-scale ensemble, for each scale s in the order given: the image resized to (scaled_size(H, s), scaled_size(W, s)) by
+    resize_image (a scale whose size is (H, W) takes the image as it is, in its own dtype); the sweep above, flip included, at that size
+    with the same tile and stride; pylc_blend_resample_accumulate, which divides that size's sums by their counts, resamples the
+    probabilities bilinearly to H x W and adds scale_weights[k] (default 1.0 each) times them into one ensemble image [H,W,cp]; the
+    scaled accumulation image is then freed.  pylc_ensemble_finalize divides by the sum of the weights.  scales=(1.0,) gives the bytes
+    of scales=None.  Memory: the ensemble image plus one scaled accumulation image, (1 + s^2) * H*W*cp*4 bytes -- on a 3072 x 4096
+    photograph with 9 classes 0.6 + 2.4 GB at s = 2 and 0.6 + 0.94 GB at 1.25.  ValueError for an empty sequence, a scale outside the
+    range, weights of another length or not positive, and a scale that takes a side of the image below `out`.
+
     `group`: every rank accumulates its share of the batches into its own image, dist.all_reduce sums them (results then differ from one
     process's by fp32 summation order only; a one-rank group equals no group bit for bit), rank 0 finalizes, the others return None.
+    With scales every rank resamples its own partial sums into its own ensemble image -- the divisor of a pixel is a constant of the
+    geometry, so the step is linear -- and one all_reduce of the ensemble image runs at the end.
     Returns mask, or (mask[, probs][, conf])."""
-    L.init()
     if stride is None:
         stride = tile // 2 if out == tile else out
     stride = int(stride)
+    if scales is None and scale_weights is not None:
+        raise ValueError('scale_weights needs scales')
+    plan = None if scales is None else ensemble_plan(scales, scale_weights, image.shape[1], image.shape[2], out)    # before any launch
+    L.init()
     dev = model.device
     u8 = image.dtype == torch.uint8
     img = image.to(dev, dtype=torch.uint8 if u8 else torch.float32).contiguous()
     cimg, h, w = img.shape
     if cimg != model.meta.ch:
         raise ValueError('model expects %d-channel images' % model.meta.ch)
-    row_o, col_o = overlap_tile_grid(h, w, out, stride, (tile - out) // 2)
-    n = len(row_o) * len(col_o)
+    overlap_tile_grid(h, w, out, stride, (tile - out) // 2)            # the geometry's errors before the network's mode is touched
     mean, std, denom = model._stats(model.meta.normalize_default)
     if denom != 255.0:                  # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
         std = [v * denom / 255.0 for v in std]
     world = dist.get_world_size(group) if group is not None else 1
     rank = dist.get_rank(group) if group is not None else 0
-    mine = shard_batches(n, batch, rank, world)
-    m = (C.c_float * 3)(*[float(v) for v in mean])
-    s = (C.c_float * 3)(*[float(v) for v in std])
+    norm = ((C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std]))
     ncls = model.meta.n_classes
     cp = (ncls + 3) & ~3
-    acc = torch.zeros((h, w, cp), device=dev)
     members = 2 if flip else 1
+    acc = ens = None
     was_training = model.net.training
     model.net.eval()
     try:
         model._refresh_for_inference()
         with torch.no_grad():
-            for member in range(members):                   # member-major: the sums of member 0 are complete before member 1 adds to them
-                for k, b in mine:
-                    x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
-                    check(lib.pylc_image_pack_tiles_reflect_ex(ptr(img), int(u8), cimg, h, w, tile, out, stride, k, b, m, s, ptr(x4), stream(),
-                                                               member))
-                    y = ops.as_nhwc(model.net(x4))                     # [b, ncls, out, out], NHWC memory
-                    if tuple(y.shape[1:]) != (ncls, out, out):
-                        raise ValueError('the network returned %s for %d px windows, not %d classes of %d px' % (tuple(y.shape), tile, ncls, out))
-                    p = ops.pitch_of(y)
-                    if p % 4 or y.data_ptr() % 16:                      # a pitch the 16-byte loads cannot take: one relayout to pitch cp
-                        y2 = ops.zeros_nhwc(b, ncls, out, out, dev, pitch=cp)
-                        y2.copy_(y)
-                        y, p = y2, cp
-                    check(lib.pylc_blend_accumulate(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream()))
+            if plan is None:
+                acc = _blend_sweep(model, img, tile, out, stride, batch, group, members, norm)
+            else:
+                ens = torch.empty((h, w, cp), device=dev)             # the first scale's launch writes every channel below ncls
+                for k, (_, hs, ws, wgt) in enumerate(plan):
+                    acc_s = _blend_sweep(model, img if (hs, ws) == (h, w) else resize_image(img, hs, ws), tile, out, stride, batch, group,
+                                         members, norm)
+                    check(lib.pylc_blend_resample_accumulate(ptr(acc_s), cp, hs, ws, out, stride, members, wgt, ncls, ptr(ens), cp, h, w,
+                                                             int(k > 0), stream()))
+                    del acc_s
     finally:
         model.net.train(was_training)
     if world > 1:
-        dist.all_reduce(acc, group=group)
+        if plan is not None:
+            ens[..., ncls:] = 0                                   # the padding channels were never written: keep the collective off garbage
+        dist.all_reduce(acc if plan is None else ens, group=group)
         if rank != 0:
             return None
-    return _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence)
+    if plan is None:
+        return _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence)
+    return _blend_finalize(ens, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, sum(p[3] for p in plan))
 
 
-def _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence):
+def _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, total_weight=None):
+    """mask[, probs][, conf] from a blend's sums (divided by the geometry's counts) or, with total_weight, from an ensemble image"""
     mask = torch.empty((h, w), device=acc.device, dtype=torch.uint8)
     probs = torch.empty((ncls, h, w), device=acc.device) if return_probs else None
     conf = torch.empty((h, w), device=acc.device) if return_confidence else None
-    check(lib.pylc_blend_finalize(ptr(acc), cp, h, w, out, stride, ncls, members, ptr(mask), ptr(probs), ptr(conf), stream()))
+    if total_weight is None:
+        check(lib.pylc_blend_finalize(ptr(acc), cp, h, w, out, stride, ncls, members, ptr(mask), ptr(probs), ptr(conf), stream()))
+    else:
+        check(lib.pylc_ensemble_finalize(ptr(acc), cp, h, w, ncls, total_weight, ptr(mask), ptr(probs), ptr(conf), stream()))
     res = (mask,) + ((probs,) if return_probs else ()) + ((conf,) if return_confidence else ())
     return res if len(res) > 1 else mask
 

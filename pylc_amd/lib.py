@@ -191,6 +191,9 @@ SIGNATURES = {
     'pylc_image_pack_tiles_reflect_ex': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P, _I]),
     'pylc_blend_accumulate': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     'pylc_blend_finalize': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'pylc_resize_bilinear_image': (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    'pylc_blend_resample_accumulate': (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _I, _I, _I, _I, _P]),
+    'pylc_ensemble_finalize': (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     'pylc_image_pack_denom': (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _F, _P, _P]),
     'pylc_image_pack_u8': (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     'pylc_extract_tiles': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

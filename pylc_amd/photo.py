@@ -228,7 +228,8 @@ def _sieve_result(res, pal, min_region, connectivity, fill, ignore_index):
 
 
 def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None, batch=8, group=None, return_probs=False, blend='reference',
-                  flip=False, return_confidence=False, min_region=0, region_connectivity=4, region_fill='neighbour', ignore_index=None):
+                  flip=False, return_confidence=False, min_region=0, region_connectivity=4, region_fill='neighbour', ignore_index=None,
+                  scales=None, scale_weights=None):
     """A decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1] grayscale uint8, numpy or tensor) -> PhotoResult at the scaled size.
 
     DeepLab, blend='reference' (default): fit (stride default tile // 2, test.py:63), predict_image's sliding window on the uint8 fitted
@@ -239,6 +240,8 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     U-Net, and DeepLab with blend='mean': the scale step only, then the mean-probability blend at the scaled size (predict_overlap_tile,
     stride default its output tile; for DeepLab predict_image(blend='mean'), stride default tile // 2); no fit, no resize back.
     return_probs / return_confidence fill PhotoResult.probs / .confidence; flip=True adds the mirrored windows as a second member.
+    scales / scale_weights: the multi-scale ensemble of predict_blend_mean on the scaled-size image, every scale in
+    [0.5, 2.0] relative to it; on a DeepLab it needs blend='mean', as flip does.
 
     min_region > 1: regions of the final mask below that many pixels are sieved (regions.sieve with region_connectivity, region_fill and
     ignore_index; one pass), PhotoResult.rgb is recoloured from the sieved mask and PhotoResult.n_sieved counts the replaced pixels.  A
@@ -256,7 +259,8 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
         raise ValueError("blend is 'reference' or 'mean', got %r" % (blend,))
     unet = model.meta.arch == 'unet'
     if not unet and blend == 'reference':
-        asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence)) if v]
+        asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence),
+                                ('scales', scales is not None), ('scale_weights', scale_weights is not None)) if v]
         if asked:
             raise ValueError("%s needs blend='mean' on a DeepLab: the reference sliding-window stitch mixes logits and probabilities, its "
                              "scores are not probabilities" % ', '.join(asked))
@@ -279,9 +283,10 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
                     'offset': 0}                      # Extractor.extract(fit=False): (img, w_scaled, h_scaled, 0)
             img = resize_area(_upload_photo(image, dev), h_s, w_s)      # at its own size: a relayout to [C,H,W]
             if unet:
-                got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence)
+                got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights)
             else:
-                got = predict_blend_mean(model, img, tile, tile, stride, batch, group, flip, return_probs, return_confidence)
+                got = predict_blend_mean(model, img, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales,
+                                         scale_weights)
             if got is None:
                 return None
             got = list(got) if isinstance(got, tuple) else [got]
