@@ -482,6 +482,44 @@ int pylc_bn_bwd_apply_ex(const float* dout, int dout_pitch, const float* out, in
                          const float* mean, const float* invstd, const float* gamma, const float* sums, double n, long long M,
                          int C, int relu, float* dy, int dy_pitch, float* g_out, int g_pitch, unsigned int* amax_dy,
                          const float* scale, const float* shift, const PylcBnExtra* ex, void* stream);
+/* The projection pair of a bottleneck with a downsample branch (models/backbone/resnet.py:36-51: residual = self.downsample(x);
+ * out = relu(bn3(conv3(.)) + residual), downsample = Sequential(conv1x1, BatchNorm2d) of _make_layer :88-103) as ONE BatchNorm node:
+ *     out = relu(y * scale + shift + (twin->y * twin->scale + twin->shift)),
+ * the shortcut's normalised tensor formed in registers with the expression pylc_bn_apply uses for a BatchNorm without ReLU, so `out`, the
+ * 1-bit mask and every backward result carry the bits of the two-node sequence
+ *     res = pylc_bn_apply(y_ds); out = pylc_bn_apply_ex(y, residual = res, relu, mask);
+ *     pylc_bn_bwd_reduce_ex + pylc_bn_bwd_apply_ex(g_out = g) for `y`;   pylc_bn_bwd_reduce_ex + pylc_bn_bwd_apply_ex(dout = g) for y_ds
+ * without `res` and g = relu'(out) dout ever reaching memory: 0 extra bytes per element in the forward (was 8 + 4), 32 in the backward (was
+ * 44).  All operands fp32 (y, twin->y, dout at any pitch), C % 8 == 0, ex->relu_mask set (written by the apply, read by the backward),
+ * no dropout; out / dy / twin->dy as fp32 or fp16 planes exactly as in the *_ex entry points.  The range bound of a plane `out` is the
+ * caller's: pylc_bn_affine_amax (below) returns max |twin->y * twin->scale + twin->shift| -- the maximum the two-node sequence measures
+ * while it writes `res` -- from one read of twin->y; hand it to the main BatchNorm's finalize as bound_extra and the plane scale of `out`
+ * is the two-node sequence's.
+ * Fields by entry point -- all: y, y_pitch; apply_pair: scale, shift; bwd_reduce_pair: mean, invstd, sums (out, [dgamma | dbeta] of the
+ * shortcut; its dbeta has the bits of the main one: sum g is one sum), workspace (pylc_bn_workspace_floats, NOT the main one),
+ * dy_bound_out with gamma (as pylc_bn_bwd_reduce_ex; ex->g_amax is shared); bwd_apply_pair: mean, invstd, gamma, sums, dy / dy_pitch or
+ * dy_planes / dy_plane_stride / dy_bound, amax_dy. */
+typedef struct PylcBnTwin {
+    const float* y;          int y_pitch;
+    const float* scale;      const float* shift;
+    const float* mean;       const float* invstd;         const float* gamma;
+    float* sums;             float* workspace;            unsigned int* dy_bound_out;
+    float* dy;               int dy_pitch;
+    void* dy_planes;         long long dy_plane_stride;   const unsigned int* dy_bound;
+    unsigned int* amax_dy;
+} PylcBnTwin;
+/* amax_out (zero-initialised by the caller) is max-accumulated with the float bits of max |y * scale + shift| over [M][C]: the amax_out of
+ * pylc_bn_apply(y, scale, shift, relu = 0) without its output. */
+int pylc_bn_affine_amax(const float* y, int y_pitch, const float* scale, const float* shift, long long M, int C, unsigned int* amax_out,
+                        void* stream);
+int pylc_bn_apply_pair(const float* y, int y_pitch, const float* scale, const float* shift, float* out, int out_pitch, long long M, int C,
+                       unsigned int* amax_out, const PylcBnExtra* ex, const PylcBnTwin* twin, void* stream);
+int pylc_bn_bwd_reduce_pair(const float* dout, int dout_pitch, const float* y, int y_pitch, const float* mean, const float* invstd,
+                            long long M, int C, float* sums, float* workspace, const float* gamma, double n, const PylcBnExtra* ex,
+                            unsigned int* dy_bound_out, const PylcBnTwin* twin, void* stream);
+int pylc_bn_bwd_apply_pair(const float* dout, int dout_pitch, const float* y, int y_pitch, const float* mean, const float* invstd,
+                           const float* gamma, const float* sums, double n, long long M, int C, float* dy, int dy_pitch,
+                           unsigned int* amax_dy, const PylcBnExtra* ex, const PylcBnTwin* twin, void* stream);
 /* Backward of a FROZEN BatchNorm -- mean / invstd are constants (the running statistics: pylc_bn_eval_coeffs_full) -- in one pass:
  *     g = [dropout mask * keep scale *] dout * (pre-activation > 0 if relu),   dy = gamma*invstd*g,   g_out = g (may be NULL),
  *     sums[0:C] = sum g*xhat (= dgamma), sums[C:2C] = sum g (= dbeta), xhat = (y - mean)*invstd.

@@ -85,6 +85,18 @@ struct BnEx {
     const unsigned* dout_bound;
 };
 
+// The second BatchNorm of a projection pair (TWIN instantiations, the *_pair entry points): relu(bn3(y3) + bn_ds(y_ds)) of a projection
+// bottleneck (resnet.py:36-51 with a downsample branch) as ONE node -- the shortcut's normalised tensor and the residual gradient
+// relu'(out) dout exist in registers only.  A template parameter like MS, so that today's instantiations keep their registers.
+struct BnTw {
+    const float* y; int y_pitch;                            // the shortcut conv's raw output, fp32
+    const float* scale; const float* shift;                 // bn_apply: the residual is y * scale + shift (the plain pass's expression)
+    const float* mean; const float* invstd;                 // the backward passes: xhat_ds
+    float* partial;                                         // bn_reduce: per-slab [sum g xhat_ds | sum g]
+    const float* gamma; const float* sums;                  // bn_bwd_apply: dx_ds = k_ds (g - sg - xhat_ds sgx_ds)
+    float* dy; int dy_pitch; _Float16* dy_pl; long long dy_ps; const unsigned* dy_bound; unsigned* amax_dy;
+};
+
 // ---- 1-bit ReLU masks ---------------------------------------------------------------------------------------------------------------
 // A BatchNorm with a residual input cannot recompute its ReLU mask from y alone (out = relu(y*scale + shift + residual)), so its
 // backward passes used to re-read `out` for the sign only: 4 B per element in bn_bwd_reduce AND in bn_bwd_apply (bn3 of every
@@ -135,20 +147,21 @@ __device__ __forceinline__ f32x4 relu_mask(f32x4 g, f32x4 o) {
 //   MS_Y    none, or recomputed from y (scale / shift given: out = max(y*scale + shift, 0), the forward's own expression -- no residual)
 //   MS_OUT  the fp32 `out`        MS_PLANES  the fp16-plane `out`        MS_BITS  the 1-bit mask bn_apply left (ex.mask)
 enum { MS_Y = 0, MS_OUT = 1, MS_PLANES = 2, MS_BITS = 3 };
-template <int MODE, bool EX = false, bool DROP = false, int MS = MS_Y, bool YH = false, bool AH = false>
+// TWIN (MODE 1, MS_BITS): a third sum, g * xhat_ds, over the shortcut's y of a projection pair (BnTw) in the same walk; sum g is shared.
+template <int MODE, bool EX = false, bool DROP = false, int MS = MS_Y, bool YH = false, bool AH = false, bool TWIN = false>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict__ a, int a_pitch,
                                                         const float* __restrict__ out, int out_pitch,
                                                         const float* __restrict__ y, int y_pitch,
                                                         const float* __restrict__ mean, const float* __restrict__ invstd,
                                                         int relu, Slab g, int C, float* __restrict__ partial,
-                                                        const float* __restrict__ scale, const float* __restrict__ shift, BnEx ex) {
+                                                        const float* __restrict__ scale, const float* __restrict__ shift, BnEx ex, BnTw tw) {
     // Accumulation: a thread sums each batch of kRowBatch rows in fp32 and folds the batch sums into fp64 accumulators; the block combines
     // in fp64 and rounds ONCE to the fp32 partial.  (Before: fp32 all the way to the partial -- hundreds of terms per thread, an error of
     // ~sqrt(rows) 2^-24 of sum |g xhat| on sums that cancel to a small fraction of that; torch's CPU BatchNorm, the parity yardstick,
     // accumulates these sums in double.  Measured on the fixtures: tests/test_nets_gpu.py::test_error_against_fp64_truth.)
     // [sum][component][thread]: consecutive lanes write consecutive doubles (the [thread][component] layout of rounds 1-5 put a wave's 64 lanes
     // 32 bytes apart: PMC SQ_LDS_BANK_CONFLICT 0.37 of this kernel's LDS cycles)
-    __shared__ double red[2][4][256];
+    __shared__ double red[TWIN ? 3 : 2][4][256];
     const int tx = threadIdx.x % g.cols, ty = threadIdx.x / g.cols;
     const long long r_begin = (long long)blockIdx.x * g.rows_per_slab;
     long long r_end = r_begin + g.rows_per_slab;
@@ -167,12 +180,16 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
         const int cv = cb + tx;
         const bool active = ty < g.RL && cv < g.CV;
         double d0[4] = {0.0, 0.0, 0.0, 0.0}, d1[4] = {0.0, 0.0, 0.0, 0.0};
+        [[maybe_unused]] double d2[4] = {0.0, 0.0, 0.0, 0.0};                 // TWIN: sum g * xhat_ds
         if (active) {
             f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};      // sums of the current batch of rows
             f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = {1.f, 1.f, 1.f, 1.f};
             f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sh = sc;
+            [[maybe_unused]] f32x4 s2 = {0.f, 0.f, 0.f, 0.f}, mu2 = s2, is2 = s2;
+            [[maybe_unused]] f32x4 vz[TWIN ? kRowBatch : 1];
             const bool remask = MODE == 1 && MS == MS_Y && relu;      // ReLU mask recomputed from y
             if (MODE == 1) { mu = ld4(mean + 4 * cv); is = ld4(invstd + 4 * cv); }
+            if constexpr (TWIN) { mu2 = ld4(tw.mean + 4 * cv); is2 = ld4(tw.invstd + 4 * cv); }
             if (remask) { sc = ld4(scale + 4 * cv); sh = ld4(shift + 4 * cv); }
             f32x4 va[kRowBatch], vy[kRowBatch], vo[MS == MS_OUT ? kRowBatch : 1];
             PlanesRaw vp[MS == MS_PLANES ? kRowBatch : 1];
@@ -184,6 +201,7 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
                     if constexpr (MS == MS_OUT) vo[u] = ld4(out + r * out_pitch + 4 * cv);
                     if constexpr (MS == MS_PLANES) vp[u] = planes_raw4(po, r * out_pitch + 4 * cv);
                     if constexpr (MS == MS_BITS) vm[u] = ex.mask[(r * g.CV + cv) >> 1];
+                    if constexpr (TWIN) vz[u] = ld4(tw.y + r * tw.y_pitch + 4 * cv);
                 },
                 [&](int u, long long r, bool valid) {
                     if (MODE == 0) {
@@ -200,6 +218,10 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
                             s0 += gg; s1 += gg * xh;
                             if constexpr (EX) gmax = fmaxf(fmaxf(gmax, fmaxf(fabsf(gg.x), fabsf(gg.y))), fmaxf(fabsf(gg.z), fabsf(gg.w)));
                         }
+                        if constexpr (TWIN) {      // the shortcut's reduce pass on g (its dout), relu = 0: the same terms in the same order
+                            const f32x4 xh2 = (vz[u] - mu2) * is2;
+                            if (valid) s2 += gg * xh2;
+                        }
                     }
                 },
                 [](int, long long) {},
@@ -208,15 +230,28 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
                     for (int k = 0; k < 4; ++k) { d0[k] += (double)s0[k]; d1[k] += (double)s1[k]; }
                     s0 = f32x4{0.f, 0.f, 0.f, 0.f};
                     s1 = s0;
+                    if constexpr (TWIN) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) d2[k] += (double)s2[k];
+                        s2 = s0;
+                    }
                 });
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) { red[0][k][threadIdx.x] = d0[k]; red[1][k][threadIdx.x] = d1[k]; }
+        if constexpr (TWIN) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) red[2][k][threadIdx.x] = d2[k];
+        }
         __syncthreads();
         if (ty == 0 && cv < g.CV) {
             for (int j = 1; j < g.RL; ++j) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { d0[k] += red[0][k][j * g.cols + tx]; d1[k] += red[1][k][j * g.cols + tx]; }
+                if constexpr (TWIN) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) d2[k] += red[2][k][j * g.cols + tx];
+                }
             }
             const f32x4 f0 = {(float)d0[0], (float)d0[1], (float)d0[2], (float)d0[3]};
             const f32x4 f1 = {(float)d1[0], (float)d1[1], (float)d1[2], (float)d1[3]};
@@ -225,6 +260,12 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
             // result can land directly in the adjacent (gamma, beta) slots of the flat gradient arena
             st4(p + 4 * cv, MODE == 0 ? f0 : f1);
             st4(p + C + 4 * cv, MODE == 0 ? f1 : f0);
+            if constexpr (TWIN) {            // the shortcut's partials, in the layout its own reduce pass writes: sum g is the same value
+                const f32x4 f2 = {(float)d2[0], (float)d2[1], (float)d2[2], (float)d2[3]};
+                float* p2 = tw.partial + (size_t)blockIdx.x * 2 * C;
+                st4(p2 + 4 * cv, f2);
+                st4(p2 + C + 4 * cv, f0);
+            }
         }
         __syncthreads();
     }
@@ -446,11 +487,13 @@ __global__ void bn_eval_coeffs_kernel(const float* rm, const float* rv, const fl
 }
 
 // ---- elementwise -------------------------------------------------------------------------------
-template <bool EX = false, bool DROP = false, bool BITS = false, bool YH = false>
+// TWIN: the residual is the shortcut BatchNorm of a projection pair applied in registers, tw.y * tw.scale + tw.shift (BnTw) -- the
+// expression of this kernel's own no-ReLU pass, so the sum has the bits it has with that pass's output read back as `res`.
+template <bool EX = false, bool DROP = false, bool BITS = false, bool YH = false, bool TWIN = false>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ y, int y_pitch,
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
                                                        const float* __restrict__ res, int res_pitch, float* __restrict__ out,
-                                                       int out_pitch, int relu, Slab g, unsigned* __restrict__ amax_out, BnEx ex) {
+                                                       int out_pitch, int relu, Slab g, unsigned* __restrict__ amax_out, BnEx ex, BnTw tw) {
     const int tx = threadIdx.x % g.cols, ty = threadIdx.x / g.cols;
     const long long r_begin = (long long)blockIdx.x * g.rows_per_slab;
     long long r_end = r_begin + g.rows_per_slab;
@@ -473,19 +516,27 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     if (ty < g.RL) {
         for (int cv = tx; cv < g.CV; cv += g.cols) {
             const f32x4 sc = ld4(scale + 4 * cv), sh = ld4(shift + 4 * cv);
+            [[maybe_unused]] f32x4 sc2 = {0.f, 0.f, 0.f, 0.f}, sh2 = sc2;
+            if constexpr (TWIN) { sc2 = ld4(tw.scale + 4 * cv); sh2 = ld4(tw.shift + 4 * cv); }
             f32x4 vy[kRowBatch], vr[kRowBatch];
             PlanesRaw vp[EX ? kRowBatch : 1];
             unsigned nb[BITS ? kRowBatch : 1];
             walk_rows(r_begin + ty, r_end, g.RL,
                 [&](int u, long long r) {
                     vy[u] = ldq<YH>(y, (size_t)(r * y_pitch + 4 * cv), y_inv);
-                    if (res != nullptr) vr[u] = ld4(res + r * res_pitch + 4 * cv);
-                    if constexpr (EX) { if (res_pl) vp[u] = planes_raw4(pr, r * res_pitch + 4 * cv); }
+                    if constexpr (TWIN) vr[u] = ld4(tw.y + r * tw.y_pitch + 4 * cv);
+                    else {
+                        if (res != nullptr) vr[u] = ld4(res + r * res_pitch + 4 * cv);
+                        if constexpr (EX) { if (res_pl) vp[u] = planes_raw4(pr, r * res_pitch + 4 * cv); }
+                    }
                 },
                 [&](int u, long long r, bool valid) {
                     f32x4 v = vy[u] * sc + sh;
-                    if (res != nullptr) v += vr[u];
-                    if constexpr (EX) { if (res_pl) v += planes_value4(vp[u], res_inv); }
+                    if constexpr (TWIN) v += vr[u] * sc2 + sh2;
+                    else {
+                        if (res != nullptr) v += vr[u];
+                        if constexpr (EX) { if (res_pl) v += planes_value4(vp[u], res_inv); }
+                    }
                     if constexpr (BITS) nb[u] = relu_nibble(v);
                     if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                     if constexpr (DROP) v = drop4(dr, r, g.CV, cv, v);
@@ -502,10 +553,38 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     if (amax_out != nullptr) amax_commit(amax, amax_out);      // range of the output for the f16x3 conv that consumes it
 }
 
+// Range of y * scale + shift WITHOUT writing it: max |.| of the values bn_apply_kernel's plain no-ReLU pass would store (its expression, its
+// amax), for the shortcut of a projection pair whose normalised tensor exists in registers only -- the residual's part of the plane
+// output's bound is then the number the two-node path measures, and the plane scale of the block output does not move.  One read of y.
+__global__ __launch_bounds__(256) void bn_affine_amax_kernel(const float* __restrict__ y, int y_pitch, const float* __restrict__ scale,
+                                                             const float* __restrict__ shift, Slab g, unsigned* __restrict__ amax_out) {
+    const int tx = threadIdx.x % g.cols, ty = threadIdx.x / g.cols;
+    const long long r_begin = (long long)blockIdx.x * g.rows_per_slab;
+    long long r_end = r_begin + g.rows_per_slab;
+    if (r_end > g.M) r_end = g.M;
+    float amax = 0.f;
+    if (ty < g.RL) {
+        for (int cv = tx; cv < g.CV; cv += g.cols) {
+            const f32x4 sc = ld4(scale + 4 * cv), sh = ld4(shift + 4 * cv);
+            f32x4 vy[2 * kRowBatch];
+            walk_rows<2 * kRowBatch>(r_begin + ty, r_end, g.RL,
+                [&](int u, long long r) { vy[u] = ld4(y + r * y_pitch + 4 * cv); },
+                [&](int u, long long, bool valid) {
+                    const f32x4 v = vy[u] * sc + sh;
+                    if (valid) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+                },
+                [](int, long long) {});
+        }
+    }
+    amax_commit(amax, amax_out);
+}
+
 // EX: `out` (ReLU mask) may be an fp16-plane tensor, the forward's dropout is regenerated, dy may be written as fp16 planes scaled
 // with the bound in ex.dy_bound (bn_bwd_sums_kernel).
-template <bool EX = false, bool DROP = false, int MS = MS_Y, bool YH = false, bool AH = false>
-__global__ __launch_bounds__(256, 3) void bn_bwd_apply_kernel(const float* __restrict__ dout, int dout_pitch,
+// TWIN (MS_BITS): the same walk also writes the shortcut BatchNorm's dy of a projection pair (BnTw: fp32 or planes with its own bound) from
+// g and the shortcut's y, each with the per-element expression of its own pass; g itself is not written.
+template <bool EX = false, bool DROP = false, int MS = MS_Y, bool YH = false, bool AH = false, bool TWIN = false>
+__global__ __launch_bounds__(256, TWIN ? 2 : 3) void bn_bwd_apply_kernel(const float* __restrict__ dout, int dout_pitch,
                                                            const float* __restrict__ out, int out_pitch,
                                                            const float* __restrict__ y, int y_pitch,
                                                            const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -513,7 +592,7 @@ __global__ __launch_bounds__(256, 3) void bn_bwd_apply_kernel(const float* __res
                                                            float inv_n, int C, int relu, float* __restrict__ dy, int dy_pitch,
                                                            float* __restrict__ g_out, int g_pitch, Slab g,
                                                            unsigned* __restrict__ amax_dy, const float* __restrict__ scale,
-                                                           const float* __restrict__ shift, BnEx ex) {
+                                                           const float* __restrict__ shift, BnEx ex, BnTw tw) {
     const int tx = threadIdx.x % g.cols, ty = threadIdx.x / g.cols;
     const long long r_begin = (long long)blockIdx.x * g.rows_per_slab;
     long long r_end = r_begin + g.rows_per_slab;
@@ -527,6 +606,9 @@ __global__ __launch_bounds__(256, 3) void bn_bwd_apply_kernel(const float* __res
         dr = DropRef{ex.drop_thresh, ex.keep_scale, ex.seed};
     }
     const bool dy_pl = EX && pd.base != nullptr;
+    [[maybe_unused]] PlanesRef pd2{};
+    [[maybe_unused]] float amax2 = 0.f;
+    if constexpr (TWIN) { if (tw.dy_pl != nullptr) pd2 = PlanesRef{tw.dy_pl, tw.dy_ps, ex.nplanes, pow2_scale_for(*tw.dy_bound)}; }
     float a_inv = 1.f, y_inv = 1.f, g_scale = 1.f;
     if constexpr (AH) { a_inv = 1.f / half_scale_for(*ex.dout_bound); g_scale = half_scale_for(*ex.dout_bound); }
     if constexpr (YH) y_inv = 1.f / half_scale_for(*ex.y_bound);
@@ -538,10 +620,18 @@ __global__ __launch_bounds__(256, 3) void bn_bwd_apply_kernel(const float* __res
             const bool remask = MS == MS_Y && relu;
             f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sh = sc;
             if (remask) { sc = ld4(scale + 4 * cv); sh = ld4(shift + 4 * cv); }
+            [[maybe_unused]] f32x4 mu2 = sc, is2 = sc, k2 = sc, sgx2 = sc, sg2 = sc;
+            if constexpr (TWIN) {
+                mu2 = ld4(tw.mean + 4 * cv); is2 = ld4(tw.invstd + 4 * cv);
+                k2 = ld4(tw.gamma + 4 * cv) * is2;
+                sgx2 = ld4(tw.sums + 4 * cv) * inv_n; sg2 = ld4(tw.sums + C + 4 * cv) * inv_n;
+            }
             constexpr int NB = 4;            // 4 rows x 2-3 tensors in flight per wave; <= 168 registers = 3 waves per SIMD = the 3 blocks per CU of a 768-slab launch
+                                             // (TWIN: a third tensor and a second set of coefficients -- 2 blocks per CU, what a 512-slab launch runs)
             f32x4 vg[NB], vy[NB], vo[MS == MS_OUT ? NB : 1];
             PlanesRaw vp[MS == MS_PLANES ? NB : 1];
             unsigned vm[MS == MS_BITS ? NB : 1];
+            [[maybe_unused]] f32x4 vz[TWIN ? NB : 1];
             walk_rows<NB>(r_begin + ty, r_end, g.RL,
                 [&](int u, long long r) {
                     vg[u] = ldq<AH>(dout, (size_t)(r * dout_pitch + 4 * cv), a_inv);
@@ -549,6 +639,7 @@ __global__ __launch_bounds__(256, 3) void bn_bwd_apply_kernel(const float* __res
                     if constexpr (MS == MS_OUT) vo[u] = ld4(out + r * out_pitch + 4 * cv);
                     if constexpr (MS == MS_PLANES) vp[u] = planes_raw4(po, r * out_pitch + 4 * cv);
                     if constexpr (MS == MS_BITS) vm[u] = ex.mask[(r * g.CV + cv) >> 1];
+                    if constexpr (TWIN) vz[u] = ld4(tw.y + r * tw.y_pitch + 4 * cv);
                 },
                 [&](int u, long long r, bool valid) {
                     f32x4 gg = vg[u];
@@ -562,15 +653,26 @@ __global__ __launch_bounds__(256, 3) void bn_bwd_apply_kernel(const float* __res
                     vg[u] = gg;                                      // the masked gradient (residual branch) and dy, kept for the store pass
                     vy[u] = v;
                     if (valid) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+                    if constexpr (TWIN) {
+                        const f32x4 xh2 = (vz[u] - mu2) * is2;
+                        const f32x4 v2 = k2 * (gg - sg2 - xh2 * sgx2);
+                        vz[u] = v2;
+                        if (valid) amax2 = fmaxf(fmaxf(amax2, fmaxf(fabsf(v2.x), fabsf(v2.y))), fmaxf(fabsf(v2.z), fabsf(v2.w)));
+                    }
                 },
                 [&](int u, long long r) {
-                    if (g_out != nullptr) stq<AH>(g_out, (size_t)(r * g_pitch + 4 * cv), vg[u], g_scale);
+                    if constexpr (!TWIN) { if (g_out != nullptr) stq<AH>(g_out, (size_t)(r * g_pitch + 4 * cv), vg[u], g_scale); }
                     if (dy_pl) { if constexpr (EX) planes_store4(pd, r * dy_pitch + 4 * cv, vy[u]); }
                     else st4(dy + r * dy_pitch + 4 * cv, vy[u]);
+                    if constexpr (TWIN) {
+                        if (pd2.base != nullptr) planes_store4(pd2, r * tw.dy_pitch + 4 * cv, vz[u]);
+                        else st4(tw.dy + r * tw.dy_pitch + 4 * cv, vz[u]);
+                    }
                 });
         }
     }
     if (amax_dy != nullptr) amax_commit(amax, amax_dy);
+    if constexpr (TWIN) { if (tw.amax_dy != nullptr) amax_commit(amax2, tw.amax_dy); }
 }
 
 // Backward of a FROZEN BatchNorm (constant statistics: the running mean / variance of a loaded model) in ONE walk.  With mean and invstd
@@ -833,7 +935,7 @@ extern "C" int pylc_bn_stats(const float* y, long long M, int C, int y_pitch, fl
     const Slab g = make_slab(M, C);
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL((bn_reduce_kernel<0>), dim3(g.nslab), dim3(256), 0, st, y, y_pitch, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, g, C,
-                       workspace, nullptr, nullptr, BnEx{});
+                       workspace, nullptr, nullptr, BnEx{}, BnTw{});
     PYLC_LAUNCH_CHECK();
     hipLaunchKernelGGL(column_sum_kernel, dim3(cdiv(2 * C, 8)), dim3(256), 0, st, workspace, g.nslab, 2 * C, sums);
     PYLC_LAUNCH_CHECK();
@@ -949,22 +1051,22 @@ extern "C" int pylc_bn_apply_ex(const float* y, int y_pitch, const float* scale,
         PYLC_REQUIRE(!(bits && drop), "bn_apply: the 1-bit ReLU mask and fused dropout are not combined");
 #define PYLC_BN_APPLY_H(DROPV, BITSV)                                                                                                    \
         hipLaunchKernelGGL((bn_apply_kernel<true, DROPV, BITSV, true>), dim3(g.nslab), dim3(256), 0, as_stream(stream), y, y_pitch, scale, shift, residual, \
-                           res_pitch, out, out_pitch, relu, g, amax_out, make_ex(ex))
+                           res_pitch, out, out_pitch, relu, g, amax_out, make_ex(ex), BnTw{})
         if (bits) PYLC_BN_APPLY_H(false, true); else if (drop) PYLC_BN_APPLY_H(true, false); else PYLC_BN_APPLY_H(false, false);
 #undef PYLC_BN_APPLY_H
     } else if (ex != nullptr && ex->relu_mask != nullptr && relu) {
         PYLC_REQUIRE(!(ex->drop_p > 0.f), "bn_apply: the 1-bit ReLU mask and fused dropout are not combined");
         hipLaunchKernelGGL((bn_apply_kernel<true, false, true>), dim3(g.nslab), dim3(256), 0, as_stream(stream), y, y_pitch, scale, shift, residual, res_pitch,
-                           out, out_pitch, relu, g, amax_out, make_ex(ex));
+                           out, out_pitch, relu, g, amax_out, make_ex(ex), BnTw{});
     } else if (ex != nullptr && ex->drop_p > 0.f)
         hipLaunchKernelGGL((bn_apply_kernel<true, true>), dim3(g.nslab), dim3(256), 0, as_stream(stream), y, y_pitch, scale, shift, residual, res_pitch,
-                           out, out_pitch, relu, g, amax_out, make_ex(ex));
+                           out, out_pitch, relu, g, amax_out, make_ex(ex), BnTw{});
     else if (ex != nullptr)
         hipLaunchKernelGGL((bn_apply_kernel<true, false>), dim3(g.nslab), dim3(256), 0, as_stream(stream), y, y_pitch, scale, shift, residual, res_pitch,
-                           out, out_pitch, relu, g, amax_out, make_ex(ex));
+                           out, out_pitch, relu, g, amax_out, make_ex(ex), BnTw{});
     else
         hipLaunchKernelGGL((bn_apply_kernel<false>), dim3(g.nslab), dim3(256), 0, as_stream(stream), y, y_pitch, scale, shift, residual, res_pitch,
-                           out, out_pitch, relu, g, amax_out, BnEx{});
+                           out, out_pitch, relu, g, amax_out, BnEx{}, BnTw{});
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
 }
@@ -995,10 +1097,10 @@ extern "C" int pylc_bn_bwd_reduce_ex(const float* dout, int dout_pitch, const fl
     const bool yh = ex != nullptr && ex->y_half_bound != nullptr, ah = ex != nullptr && ex->dout_half_bound != nullptr;      // one-plane fp16 y / dout (precision mode 3)
 #define PYLC_BN_REDUCE(EXV, DROPV, MSV)                                                                                                   \
     hipLaunchKernelGGL((bn_reduce_kernel<1, EXV, DROPV, MSV>), dim3(g.nslab), dim3(256), 0, st, dout, dout_pitch, out, out_pitch, y, y_pitch, mean, \
-                       invstd, relu, g, C, workspace, scale, shift, ex ? make_ex(ex) : BnEx{})
+                       invstd, relu, g, C, workspace, scale, shift, ex ? make_ex(ex) : BnEx{}, BnTw{})
 #define PYLC_BN_REDUCE_H2(DROPV, MSV, YHV, AHV)                                                                                           \
     hipLaunchKernelGGL((bn_reduce_kernel<1, true, DROPV, MSV, YHV, AHV>), dim3(g.nslab), dim3(256), 0, st, dout, dout_pitch, out, out_pitch, y, y_pitch, mean, \
-                       invstd, relu, g, C, workspace, scale, shift, make_ex(ex))
+                       invstd, relu, g, C, workspace, scale, shift, make_ex(ex), BnTw{})
 #define PYLC_BN_REDUCE_H(DROPV, MSV)                                                                                                      \
     { if (yh && ah) PYLC_BN_REDUCE_H2(DROPV, MSV, true, true); else if (yh) PYLC_BN_REDUCE_H2(DROPV, MSV, true, false); else PYLC_BN_REDUCE_H2(DROPV, MSV, false, true); }
     if (yh || ah) {
@@ -1086,13 +1188,13 @@ extern "C" int pylc_bn_bwd_apply_ex(const float* dout, int dout_pitch, const flo
     const bool yh = ex != nullptr && ex->y_half_bound != nullptr, ah = ex != nullptr && ex->dout_half_bound != nullptr;      // one-plane fp16 y / dout (+ g_out)
 #define PYLC_BN_BWD_APPLY_H2(DROPV, MSV, YHV, AHV)                                                                                        \
     hipLaunchKernelGGL((bn_bwd_apply_kernel<true, DROPV, MSV, YHV, AHV>), dim3(g.nslab), dim3(256), 0, as_stream(stream), dout, dout_pitch, out, out_pitch, y, \
-                       y_pitch, mean, invstd, gamma, sums, (float)(1.0 / n), C, relu, dy, dy_pitch, g_out, g_pitch, g, amax_dy, scale, shift, make_ex(ex))
+                       y_pitch, mean, invstd, gamma, sums, (float)(1.0 / n), C, relu, dy, dy_pitch, g_out, g_pitch, g, amax_dy, scale, shift, make_ex(ex), BnTw{})
 #define PYLC_BN_BWD_APPLY_H(DROPV, MSV)                                                                                                   \
     { if (yh && ah) PYLC_BN_BWD_APPLY_H2(DROPV, MSV, true, true); else if (yh) PYLC_BN_BWD_APPLY_H2(DROPV, MSV, true, false); else PYLC_BN_BWD_APPLY_H2(DROPV, MSV, false, true); }
 #define PYLC_BN_BWD_APPLY(EXV, DROPV, MSV)                                                                                                \
     hipLaunchKernelGGL((bn_bwd_apply_kernel<EXV, DROPV, MSV>), dim3(g.nslab), dim3(256), 0, as_stream(stream), dout, dout_pitch, out, out_pitch, y, \
                        y_pitch, mean, invstd, gamma, sums, (float)(1.0 / n), C, relu, dy, dy_pitch, g_out, g_pitch, g, amax_dy, scale, shift,       \
-                       ex ? make_ex(ex) : BnEx{})
+                       ex ? make_ex(ex) : BnEx{}, BnTw{})
     if (yh || ah) {
         PYLC_REQUIRE(ms != MS_OUT && !(drop && ms != MS_Y), "bn_bwd_apply (half operands): mask from y, the 1-bit mask or fp16-plane out; dropout with the y mask only");
         if (drop) PYLC_BN_BWD_APPLY_H(true, MS_Y) else if (ms == MS_BITS) PYLC_BN_BWD_APPLY_H(false, MS_BITS)
@@ -1117,6 +1219,111 @@ extern "C" int pylc_bn_bwd_apply(const float* dout, int dout_pitch, const float*
                                  const float* scale, const float* shift, void* stream) {
     return pylc_bn_bwd_apply_ex(dout, dout_pitch, out, out_pitch, y, y_pitch, mean, invstd, gamma, sums, n, M, C, relu, dy, dy_pitch, g_out,
                                 g_pitch, amax_dy, scale, shift, nullptr, stream);
+}
+
+// ---- projection pair: relu(bn3(y3) + bn_ds(y_ds)) as one node (TWIN instantiations) ------------------------------------------------
+static int check_twin(const PylcBnExtra* ex, const PylcBnTwin* tw, int C, const char* what) {
+    PYLC_REQUIRE(ex && tw, "%s: needs ex and twin", what);
+    PYLC_REQUIRE(ex->relu_mask && C % 8 == 0, "%s: the pair runs on the 1-bit ReLU mask (C %% 8 == 0, C=%d)", what, C);
+    PYLC_REQUIRE(!(ex->drop_p > 0.f) && !ex->res_planes && !ex->y_half_bound && !ex->dout_half_bound,
+                 "%s: no dropout, no plane residual, fp32 y / dout only", what);
+    PYLC_REQUIRE(tw->y && tw->y_pitch >= C && tw->y_pitch % 4 == 0, "%s: bad shortcut y / pitch", what);
+    return PYLC_OK;
+}
+
+extern "C" int pylc_bn_affine_amax(const float* y, int y_pitch, const float* scale, const float* shift, long long M, int C,
+                                   unsigned int* amax_out, void* stream) {
+    if (int rc = check_mc(M, C, y_pitch, "bn_affine_amax")) return rc;
+    PYLC_REQUIRE(y && scale && shift && amax_out, "bn_affine_amax: null pointer");
+    const Slab g = make_slab(M, C);
+    hipLaunchKernelGGL(bn_affine_amax_kernel, dim3(g.nslab), dim3(256), 0, as_stream(stream), y, y_pitch, scale, shift, g, amax_out);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_bn_apply_pair(const float* y, int y_pitch, const float* scale, const float* shift, float* out, int out_pitch,
+                                  long long M, int C, unsigned int* amax_out, const PylcBnExtra* ex, const PylcBnTwin* twin,
+                                  void* stream) {
+    if (int rc = check_mc(M, C, y_pitch, "bn_apply_pair")) return rc;
+    if (int rc = check_mc(M, C, out_pitch, "bn_apply_pair(out)")) return rc;
+    if (int rc = check_ex(ex, C, "bn_apply_pair")) return rc;
+    if (int rc = check_twin(ex, twin, C, "bn_apply_pair")) return rc;
+    const bool out_pl = ex->out_planes != nullptr;
+    PYLC_REQUIRE(y && scale && shift && twin->scale && twin->shift && (out != nullptr) != out_pl,
+                 "bn_apply_pair: null pointer (exactly one of out / ex->out_planes)");
+    PYLC_REQUIRE(!out_pl || ex->out_bound, "bn_apply_pair: planes output needs out_bound");
+    const Slab g = make_slab(M, C);
+    BnTw tw{};
+    tw.y = twin->y; tw.y_pitch = twin->y_pitch; tw.scale = twin->scale; tw.shift = twin->shift;
+    hipLaunchKernelGGL((bn_apply_kernel<true, false, true, false, true>), dim3(g.nslab), dim3(256), 0, as_stream(stream), y, y_pitch, scale, shift,
+                       nullptr, 0, out, out_pitch, 1, g, amax_out, make_ex(ex), tw);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_bn_bwd_reduce_pair(const float* dout, int dout_pitch, const float* y, int y_pitch, const float* mean,
+                                       const float* invstd, long long M, int C, float* sums, float* workspace, const float* gamma,
+                                       double n, const PylcBnExtra* ex, unsigned int* dy_bound_out, const PylcBnTwin* twin,
+                                       void* stream) {
+    if (int rc = check_mc(M, C, dout_pitch, "bn_bwd_reduce_pair")) return rc;
+    if (int rc = check_mc(M, C, y_pitch, "bn_bwd_reduce_pair(y)")) return rc;
+    if (int rc = check_ex(ex, C, "bn_bwd_reduce_pair")) return rc;
+    if (int rc = check_twin(ex, twin, C, "bn_bwd_reduce_pair")) return rc;
+    PYLC_REQUIRE(dout && y && mean && invstd && sums && workspace && twin->mean && twin->invstd && twin->sums && twin->workspace &&
+                 twin->workspace != workspace, "bn_bwd_reduce_pair: null pointer (each BatchNorm has its own sums and workspace)");
+    PYLC_REQUIRE(!(dy_bound_out || twin->dy_bound_out) || (ex->g_amax && n > 0), "bn_bwd_reduce_pair: a dy bound needs ex->g_amax and n");
+    PYLC_REQUIRE(!dy_bound_out || gamma, "bn_bwd_reduce_pair: the dy bound needs gamma");
+    PYLC_REQUIRE(!twin->dy_bound_out || twin->gamma, "bn_bwd_reduce_pair: the shortcut's dy bound needs its gamma");
+    const Slab g = make_slab(M, C);
+    hipStream_t st = as_stream(stream);
+    BnTw tw{};
+    tw.y = twin->y; tw.y_pitch = twin->y_pitch; tw.mean = twin->mean; tw.invstd = twin->invstd; tw.partial = twin->workspace;
+    hipLaunchKernelGGL((bn_reduce_kernel<1, true, false, MS_BITS, false, false, true>), dim3(g.nslab), dim3(256), 0, st, dout, dout_pitch, nullptr, 0, y,
+                       y_pitch, mean, invstd, 1, g, C, workspace, nullptr, nullptr, make_ex(ex), tw);
+    PYLC_LAUNCH_CHECK();
+    // the combine of each BatchNorm's own reduce pass, on partials laid out as that pass lays them out: the per-channel bits are its bits
+    if (dy_bound_out != nullptr)
+        hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(C, 8)), dim3(256), 0, st, workspace, g.nslab, C, sums, gamma, invstd, n, ex->g_amax,
+                           dy_bound_out);
+    else
+        hipLaunchKernelGGL(column_sum_kernel, dim3(cdiv(2 * C, 8)), dim3(256), 0, st, workspace, g.nslab, 2 * C, sums);
+    PYLC_LAUNCH_CHECK();
+    if (twin->dy_bound_out != nullptr)
+        hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3(cdiv(C, 8)), dim3(256), 0, st, twin->workspace, g.nslab, C, twin->sums, twin->gamma,
+                           twin->invstd, n, ex->g_amax, twin->dy_bound_out);
+    else
+        hipLaunchKernelGGL(column_sum_kernel, dim3(cdiv(2 * C, 8)), dim3(256), 0, st, twin->workspace, g.nslab, 2 * C, twin->sums);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_bn_bwd_apply_pair(const float* dout, int dout_pitch, const float* y, int y_pitch, const float* mean,
+                                      const float* invstd, const float* gamma, const float* sums, double n, long long M, int C,
+                                      float* dy, int dy_pitch, unsigned int* amax_dy, const PylcBnExtra* ex, const PylcBnTwin* twin,
+                                      void* stream) {
+    if (int rc = check_mc(M, C, dout_pitch, "bn_bwd_apply_pair")) return rc;
+    if (int rc = check_mc(M, C, y_pitch, "bn_bwd_apply_pair(y)")) return rc;
+    if (int rc = check_mc(M, C, dy_pitch, "bn_bwd_apply_pair(dy)")) return rc;
+    if (int rc = check_ex(ex, C, "bn_bwd_apply_pair")) return rc;
+    if (int rc = check_twin(ex, twin, C, "bn_bwd_apply_pair")) return rc;
+    const bool dy_pl = ex->dy_planes != nullptr, dy2_pl = twin->dy_planes != nullptr;
+    PYLC_REQUIRE(dout && y && mean && invstd && gamma && sums && n > 0 && (dy != nullptr) != dy_pl,
+                 "bn_bwd_apply_pair: bad arguments (exactly one of dy / ex->dy_planes)");
+    PYLC_REQUIRE(twin->mean && twin->invstd && twin->gamma && twin->sums && (twin->dy != nullptr) != dy2_pl,
+                 "bn_bwd_apply_pair: bad shortcut arguments (exactly one of twin->dy / twin->dy_planes)");
+    PYLC_REQUIRE(!dy2_pl || (twin->dy_bound && (ex->nplanes == 1 || twin->dy_plane_stride > 0) &&
+                             (reinterpret_cast<uintptr_t>(twin->dy_planes) & 7) == 0), "bn_bwd_apply_pair: shortcut dy planes need dy_bound, a stride and 8-byte alignment");
+    if (int rc = check_mc(M, C, twin->dy_pitch, "bn_bwd_apply_pair(shortcut dy)")) return rc;
+    const Slab g = make_slab(M, C);
+    BnTw tw{};
+    tw.y = twin->y; tw.y_pitch = twin->y_pitch; tw.mean = twin->mean; tw.invstd = twin->invstd; tw.gamma = twin->gamma; tw.sums = twin->sums;
+    tw.dy = twin->dy; tw.dy_pitch = twin->dy_pitch; tw.dy_pl = static_cast<_Float16*>(twin->dy_planes); tw.dy_ps = twin->dy_plane_stride;
+    tw.dy_bound = twin->dy_bound; tw.amax_dy = twin->amax_dy;
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, false, MS_BITS, false, false, true>), dim3(g.nslab), dim3(256), 0, as_stream(stream), dout, dout_pitch,
+                       nullptr, 0, y, y_pitch, mean, invstd, gamma, sums, (float)(1.0 / n), C, 1, dy, dy_pitch, nullptr, 0, g, amax_dy, nullptr, nullptr,
+                       make_ex(ex), tw);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
 }
 
 extern "C" int pylc_bn_frozen_bwd(const float* dout, int dout_pitch, const float* out, int out_pitch, const float* y, int y_pitch,

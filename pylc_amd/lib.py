@@ -46,6 +46,13 @@ class BnExtra(C.Structure):
                 ('nplanes', C.c_int), ('drop_p', C.c_float), ('drop_seed', C.c_uint64), ('g_amax', C.c_void_p), ('relu_mask', C.c_void_p), ('y_half_bound', C.c_void_p), ('dout_half_bound', C.c_void_p)]
 
 
+class BnTwin(C.Structure):
+    """PylcBnTwin: the shortcut BatchNorm of a projection pair (the pylc_bn_*_pair entry points)."""
+    _fields_ = [('y', C.c_void_p), ('y_pitch', C.c_int), ('scale', C.c_void_p), ('shift', C.c_void_p), ('mean', C.c_void_p), ('invstd', C.c_void_p),
+                ('gamma', C.c_void_p), ('sums', C.c_void_p), ('workspace', C.c_void_p), ('dy_bound_out', C.c_void_p), ('dy', C.c_void_p),
+                ('dy_pitch', C.c_int), ('dy_planes', C.c_void_p), ('dy_plane_stride', C.c_longlong), ('dy_bound', C.c_void_p), ('amax_dy', C.c_void_p)]
+
+
 class BnBack(C.Structure):
     """PylcBnBack: the BatchNorm whose backward sums a conv dgrad takes in its epilogue (pylc_conv2d_dgrad_bn)."""
     _fields_ = [('y', C.c_void_p), ('mean', C.c_void_p), ('invstd', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
@@ -159,6 +166,10 @@ SIGNATURES = {
     'pylc_bn_bwd_bound': (_I, [_P, _P, _P, _D, _I, _P, _P, _P]),
     'pylc_bn_bwd_apply_ex': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _D, _LL, _I, _I, _P, _I, _P, _I, _P, _P, _P,
                                   C.POINTER(BnExtra), _P]),
+    'pylc_bn_affine_amax': (_I, [_P, _I, _P, _P, _LL, _I, _P, _P]),
+    'pylc_bn_apply_pair': (_I, [_P, _I, _P, _P, _P, _I, _LL, _I, _P, C.POINTER(BnExtra), C.POINTER(BnTwin), _P]),
+    'pylc_bn_bwd_reduce_pair': (_I, [_P, _I, _P, _I, _P, _P, _LL, _I, _P, _P, _P, _D, C.POINTER(BnExtra), _P, C.POINTER(BnTwin), _P]),
+    'pylc_bn_bwd_apply_pair': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _D, _LL, _I, _P, _I, _P, C.POINTER(BnExtra), C.POINTER(BnTwin), _P]),
     'pylc_bn_apply': (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _LL, _I, _I, _P, _P]),
     'pylc_bn_bwd_reduce': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _LL, _I, _I, _P, _P, _P, _P, _P]),
     'pylc_bn_bwd_apply': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _D, _LL, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P]),

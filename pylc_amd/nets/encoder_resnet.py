@@ -8,6 +8,7 @@ from torch import nn
 
 from .. import ops
 from ..layers import Conv2d, BatchNorm2d, Named, conv_bn
+from ..runtime import runtime
 
 
 class Bottleneck(nn.Module):
@@ -36,9 +37,30 @@ class Bottleneck(nn.Module):
         out = conv_bn(self.conv1, self.bn1, x, relu=True, conv_link=link, out_planes=self.pl1, sole=True)       # read by conv2 only
         out = conv_bn(self.conv2, self.bn2, out, relu=True, out_planes=self.pl2, sole=True)                     # read by conv3 only
         if self.downsample is not None:
+            if self.pair_eligible(torch.is_grad_enabled() and (x.requires_grad or self.bn3.weight.requires_grad)):
+                return self._tail_pair(out, x, link)
             res = conv_bn(self.downsample.child(0), self.downsample.child(1), x, conv_link=link)
             return self._tail(out, res, None)
         return self._tail(out, x, link)
+
+    def pair_eligible(self, needs_grad=True):
+        """Does the projection tail run as one BatchNorm node (ops.proj_pair_eligible)?  Everything else takes the two-node path."""
+        bn3, dbn = self.bn3, self.downsample.child(1)
+        return ops.proj_pair_eligible(runtime.fuse_proj_bn, bn3.training and dbn.training, bn3.frozen or dbn.frozen,
+                                      runtime.sync_group if runtime.sync_bn else None, runtime.bn_clamp_eps, None, bn3.num_features,
+                                      not ops.half_acts(), not runtime.no_relu_bits, needs_grad)
+
+    def _tail_pair(self, out, x, link):
+        # relu(bn3(conv3(.)) + bn_ds(conv_ds(x))) as ONE BatchNorm node: the shortcut's normalised tensor and, in the backward, the
+        # residual gradient exist in registers only (ops.BnPairFn)
+        dconv, dbn, bn3 = self.downsample.child(0), self.downsample.child(1), self.bn3
+        y_ds = dconv(x, res_link=link)
+        y3 = self.conv3(out)
+        bn3._nbt_pending += 1
+        dbn._nbt_pending += 1
+        return ops.bn_act_pair(y3, bn3.weight, bn3.bias, bn3.running_mean, bn3.running_var, bn3.eps, bn3.momentum,
+                               y_ds, dbn.weight, dbn.bias, dbn.running_mean, dbn.running_var, dbn.eps, dbn.momentum,
+                               out_planes=self.out_planes)
 
     def _tail(self, out, res, link):
         # relu(bn3(conv3(.)) + residual): one BatchNorm pass in training, the conv epilogue alone in inference

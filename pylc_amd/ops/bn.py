@@ -478,6 +478,204 @@ class FrozenBnActFn(torch.autograd.Function):
         return (dy if ctx.needs_input_grad[0] else None, dgamma, dbeta, None, None, g_out) + (None,) * 6
 
 
+def proj_pair_eligible(fuse, training, frozen, group, clamp_eps, drop, channels, fp32_y, relu_bits, needs_grad=True):
+    """May relu(bn3(y3) + bn_ds(y_ds)) of a projection bottleneck run as ONE node (BnPairFn)?  Plain values only (no tensors, no device):
+    the runtime knob; both BatchNorms in training mode and not frozen; no SyncBN group; torch's 1/sqrt(var + eps) (not the clamped form);
+    no fused dropout; C % 8 == 0 and the 1-bit ReLU masks on (the pair's backward reads the mask); y3 and y_ds fp32 (not the one-plane half
+    activations of precision mode 3); a graph that takes gradients (the mask is what the forward leaves for it).  Anything else takes the
+    two-node path."""
+    return bool(fuse and training and not frozen and group is None and not clamp_eps and drop is None and channels % 8 == 0 and fp32_y
+                and relu_bits and needs_grad)
+
+
+def _pair_finalize(y, yp, pre_sums, gamma, beta, running_mean, running_var, eps, momentum, coef, res_amax, bound, m, c, st):
+    """The statistics -> coefficients step of BnActFn._forward for a training-mode BatchNorm without a group: the same launches."""
+    mean, invstd, scale, shift = coef[:c], coef[c:2 * c], coef[2 * c:3 * c], coef[3 * c:]
+    refine_y = y if _runtime.bn_refine else None
+    partial = pre_sums if (pre_sums is not None and pre_sums.dim() == 2 and pre_sums.shape[1] == 2 * c) else None
+    kshift = getattr(partial, '_pylc_shift', None) if partial is not None else None
+    if partial is not None:
+        check(lib.pylc_bn_finalize_from_partial_ex(ptr(partial), partial.shape[0], float(m), c, ptr(gamma), ptr(beta), eps, momentum, 0,
+                                                   ptr(running_mean), ptr(running_var), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
+                                                   ptr(res_amax), 1.0, ptr(bound), ptr(refine_y), yp, m, ptr(kshift), st))
+    else:
+        sums = torch.empty(2 * c, device=y.device)                     # [sum | sumsq]
+        ws = torch.empty(lib.pylc_bn_workspace_floats(m, c), device=y.device)
+        check(lib.pylc_bn_stats(ptr(y), m, c, yp, ptr(sums), ptr(ws), st))
+        check(lib.pylc_bn_finalize_ex(ptr(sums), float(m), c, ptr(gamma), ptr(beta), eps, momentum, 0, ptr(running_mean), ptr(running_var),
+                                      ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(res_amax), 1.0, ptr(bound), ptr(refine_y), yp, m,
+                                      None, st))
+
+
+def _pair_param_grads(ctx, gi, bi, gamma, beta, tg, tb, direct, sums, c):
+    """[dgamma | dbeta] of one BatchNorm of the pair, delivered as BnActFn._backward delivers them."""
+    dgamma = dbeta = None
+    if direct:
+        _deliver_grad(gamma, tg)
+        _deliver_grad(beta, tb)
+        return None, None
+    if ctx.needs_input_grad[gi]:
+        if tg is not None:
+            tg.copy_(sums[:c])
+            dgamma = _deliver_grad(gamma, tg)
+        else:
+            dgamma = sums[:c].clone()
+    if ctx.needs_input_grad[bi]:
+        if tb is not None:
+            tb.copy_(sums[c:])
+            dbeta = _deliver_grad(beta, tb)
+        else:
+            dbeta = sums[c:].clone()
+    return dgamma, dbeta
+
+
+class BnPairFn(torch.autograd.Function):
+    """out = relu(BN3(y) + BNds(y2)): the tail of a projection bottleneck (resnet.py:36-51 with a downsample branch) as ONE node, training
+    mode, batch statistics, no group.  Both BatchNorms are finalised exactly as BnActFn does it (coefficients, running statistics, variance
+    refinement); the shortcut's normalised tensor and the residual gradient relu'(out) dout are formed in registers (pylc_bn_*_pair) and
+    never written: the results are bit for bit those of the two BnActFn nodes, the range bound of a plane output included (the maximum of
+    the shortcut's normalised values is taken by one read pass over y2, pylc_bn_affine_amax)."""
+
+    @staticmethod
+    def forward(ctx, y, y2, gamma, beta, running_mean, running_var, gamma2, beta2, running_mean2, running_var2, eps, momentum, eps2, momentum2,
+                pre_sums, pre_sums2, want_amax, out_planes, dy_planes, dy_planes2):
+        L.init()
+        ctx.set_materialize_grads(False)
+        y, y2 = as_nhwc(y), as_nhwc(y2)
+        b, c, h, w = y.shape
+        if tuple(y2.shape) != (b, c, h, w) or c % 8:
+            raise L.PylcError('bn_act_pair: shapes %s / %s (need equal shapes, C %% 8 == 0)' % (tuple(y.shape), tuple(y2.shape)))
+        m = b * h * w
+        dev = y.device
+        st = stream()
+        yp, yp2 = pitch_of(y), pitch_of(y2)
+        if m == 1:
+            raise ValueError('Expected more than 1 value per channel when training, got input size %s' % (tuple(y.shape),))
+        out_planes = bool(out_planes and planes_ok(c, m) and m >= _core.PLANES_MIN_PIXELS)
+        coef, coef2 = torch.empty(4 * c, device=dev), torch.empty(4 * c, device=dev)            # mean | invstd | scale | shift
+        bound = amax_slot(dev) if out_planes else None
+        _pair_finalize(y2, yp2, pre_sums2, gamma2, beta2, running_mean2, running_var2, eps2, momentum2, coef2, None, None, m, c, st)
+        res_amax = None
+        if out_planes:
+            # the residual's part of the output bound: max |y2 * scale2 + shift2|, the number the two-node path measures while it writes the
+            # shortcut's output -- one read of y2 (4 B per element), so that the plane scale of the block output is that path's
+            res_amax = amax_slot(dev)
+            tm = _bn_time('apply_range+proj', m, c, m * c * 4)
+            tm.__enter__()
+            check(lib.pylc_bn_affine_amax(ptr(y2), yp2, ptr(coef2[2 * c:3 * c]), ptr(coef2[3 * c:]), m, c, ptr(res_amax), st))
+            tm.__exit__()
+        _pair_finalize(y, yp, pre_sums, gamma, beta, running_mean, running_var, eps, momentum, coef, res_amax, bound, m, c, st)
+        out = empty_nhwc(b, c, h, w, dev)
+        amax = amax_slot(dev) if (want_amax and not out_planes) else None
+        mask = torch.empty(m * c // 8, dtype=torch.uint8, device=dev)
+        tm = _bn_time('apply+res+bits+proj', m, c, m * c * (4 + (2 * nplanes() if out_planes else 4) + 4 + 0.125))
+        tm.__enter__()
+        ex = _bn_extra()
+        ex.relu_mask = ptr(mask)
+        if out_planes:
+            ex.out_planes, ex.out_plane_stride, ex.out_bound = ptr(out), pstride(m, c), ptr(bound)
+        tw = L.BnTwin()
+        tw.y, tw.y_pitch, tw.scale, tw.shift = ptr(y2), yp2, ptr(coef2[2 * c:3 * c]), ptr(coef2[3 * c:])
+        check(lib.pylc_bn_apply_pair(ptr(y), yp, ptr(coef[2 * c:3 * c]), ptr(coef[3 * c:]), None if out_planes else ptr(out), c, m, c, ptr(amax),
+                                     C.byref(ex), C.byref(tw), st))
+        tm.__exit__()
+        ctx.save_for_backward(y, y2, coef, coef2, mask)
+        ctx.params = (gamma, beta, gamma2, beta2)
+        ctx.want_amax = want_amax
+        ctx.dy_pl = bool(dy_planes and planes_ok(c, m) and yp == c)
+        ctx.dy_pl2 = bool(dy_planes2 and planes_ok(c, m) and yp2 == c)
+        if out_planes:
+            ctx.mark_non_differentiable(bound)
+            return out, bound
+        if want_amax:
+            ctx.mark_non_differentiable(amax)
+            return out, amax
+        return out
+
+    @staticmethod
+    def backward(ctx, dout, *_unused):
+        if dout is None:
+            return (None,) * 20
+        y, y2, coef, coef2, mask = ctx.saved_tensors
+        gamma, beta, gamma2, beta2 = ctx.params
+        dout = as_nhwc(dout)
+        b, c, h, w = y.shape
+        m = b * h * w
+        dev = y.device
+        st = stream()
+        yp, yp2 = pitch_of(y), pitch_of(y2)
+        n = float(m)
+        # [dgamma | dbeta] of each BatchNorm go straight into the flat gradient arena when its gamma / beta own adjacent slots there
+        tg, tb, tg2, tb2 = _grad_target(gamma), _grad_target(beta), _grad_target(gamma2), _grad_target(beta2)
+        direct = (tg is not None and tb is not None and tb.data_ptr() == tg.data_ptr() + 4 * c
+                  and ctx.needs_input_grad[2] and ctx.needs_input_grad[3])
+        direct2 = (tg2 is not None and tb2 is not None and tb2.data_ptr() == tg2.data_ptr() + 4 * c
+                   and ctx.needs_input_grad[6] and ctx.needs_input_grad[7])
+        sums = torch.as_strided(tg, (2 * c,), (1,)) if direct else torch.empty(2 * c, device=dev)
+        sums2 = torch.as_strided(tg2, (2 * c,), (1,)) if direct2 else torch.empty(2 * c, device=dev)
+        ws = torch.empty(lib.pylc_bn_workspace_floats(m, c), device=dev)
+        ws2 = torch.empty(lib.pylc_bn_workspace_floats(m, c), device=dev)
+        dy_pl, dy_pl2 = ctx.dy_pl, ctx.dy_pl2
+        g_amax = amax_slot(dev) if (dy_pl or dy_pl2) else None
+        dy_bound = amax_slot(dev) if dy_pl else None
+        dy_bound2 = amax_slot(dev) if dy_pl2 else None
+        ex = _bn_extra()
+        ex.relu_mask, ex.g_amax = ptr(mask), ptr(g_amax)
+        tw = L.BnTwin()
+        tw.y, tw.y_pitch, tw.mean, tw.invstd, tw.gamma = ptr(y2), yp2, ptr(coef2[:c]), ptr(coef2[c:2 * c]), ptr(gamma2)
+        tw.sums, tw.workspace, tw.dy_bound_out = ptr(sums2), ptr(ws2), ptr(dy_bound2)
+        # one walk over dout, the mask bits, y and y2 (12 1/8 B per element) where the two nodes read (dout, bits, y) and (g, y2)
+        tm = _bn_time('bwd_reduce(+sums)+proj', m, c, m * c * (12 + 0.125))
+        tm.__enter__()
+        check(lib.pylc_bn_bwd_reduce_pair(ptr(dout), pitch_of(dout), ptr(y), yp, ptr(coef[:c]), ptr(coef[c:2 * c]), m, c, ptr(sums), ptr(ws),
+                                          ptr(gamma), n, C.byref(ex), ptr(dy_bound), C.byref(tw), st))
+        tm.__exit__()
+        dy, dy2 = empty_nhwc(b, c, h, w, dev), empty_nhwc(b, c, h, w, dev)
+        amax_dy = amax_slot(dev) if (ctx.want_amax and not dy_pl) else None
+        amax_dy2 = amax_slot(dev) if (ctx.want_amax and not dy_pl2) else None
+        tm = _bn_time('bwd_apply+proj', m, c, m * c * (12 + 0.125 + (2 * nplanes() if dy_pl else 4) + (2 * nplanes() if dy_pl2 else 4)))
+        tm.__enter__()
+        if dy_pl:
+            ex.dy_planes, ex.dy_plane_stride, ex.dy_bound = ptr(dy), pstride(m, c), ptr(dy_bound)
+        if dy_pl2:
+            tw.dy_planes, tw.dy_plane_stride, tw.dy_bound = ptr(dy2), pstride(m, c), ptr(dy_bound2)
+        else:
+            tw.dy = ptr(dy2)
+        tw.dy_pitch, tw.amax_dy = c, ptr(amax_dy2)
+        check(lib.pylc_bn_bwd_apply_pair(ptr(dout), pitch_of(dout), ptr(y), yp, ptr(coef[:c]), ptr(coef[c:2 * c]), ptr(gamma), ptr(sums), n, m, c,
+                                         None if dy_pl else ptr(dy), c, ptr(amax_dy), C.byref(ex), C.byref(tw), st))
+        tm.__exit__()
+        for t, pl, bnd, amx in ((dy, dy_pl, dy_bound, amax_dy), (dy2, dy_pl2, dy_bound2, amax_dy2)):
+            if pl:
+                mark_planes(t, bnd)     # the conv backward that receives it reads it as planes (each y has ONE consumer, this node)
+            elif amx is not None:
+                tag_amax(t, amx)
+            t._pylc_zero_colsum = True    # batch statistics: each dy sums to zero over the rows of every channel
+        dgamma, dbeta = _pair_param_grads(ctx, 2, 3, gamma, beta, tg, tb, direct, sums, c)
+        dgamma2, dbeta2 = _pair_param_grads(ctx, 6, 7, gamma2, beta2, tg2, tb2, direct2, sums2, c)
+        return (dy, dy2, dgamma, dbeta, None, None, dgamma2, dbeta2) + (None,) * 12
+
+
+def bn_act_pair(y, gamma, beta, running_mean, running_var, eps, momentum, y2, gamma2, beta2, running_mean2, running_var2, eps2, momentum2,
+                out_planes=False):
+    """relu(BN(y) + BN2(y2)) of a projection bottleneck as one node (BnPairFn); callers check proj_pair_eligible first.  Tags and marks the
+    output as bn_act does."""
+    pre, pre2 = getattr(y, '_pylc_sums', None), getattr(y2, '_pylc_sums', None)
+    dy_ok = not _runtime.no_planes and _runtime.planes_dy
+    dy_pl, dy_pl2 = bool(getattr(y, '_pylc_dy_pl', False)) and dy_ok, bool(getattr(y2, '_pylc_dy_pl', False)) and dy_ok
+    ranged = ranges_needed()
+    out_planes = bool(out_planes) and ranged and not _runtime.no_planes
+    args = (y, y2, gamma, beta, running_mean, running_var, gamma2, beta2, running_mean2, running_var2, eps, momentum, eps2, momentum2, pre, pre2)
+    if not ranged:
+        return BnPairFn.apply(*args, False, False, False, False)
+    out, tagv = BnPairFn.apply(*args, True, out_planes, dy_pl, dy_pl2)
+    if is_planes_candidate(out_planes, True, y):
+        mark_planes(out, tagv)
+    else:
+        tag_amax(out, tagv)
+    return out
+
+
 def _drive_collectives(gens, group):
     """Run BatchNorm generators (BnActFn._forward / _backward) in lockstep: whatever they yield in one round is all-reduced as ONE message
     (a lone generator: its own tensor, no copy).  Returns their return values."""

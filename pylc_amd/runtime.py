@@ -47,6 +47,9 @@ class _Runtime:
         # PYLC_RUNTIME=fuse_res_grad=0: BatchNorms behind a residual add write the residual's gradient out (and the block's first conv dgrad
         # accumulates into it) instead of parking (dout, mask) for that dgrad's epilogue (A/B knob)
         self.fuse_res_grad = True
+        # projection bottlenecks: bn3 and the shortcut's BatchNorm run as ONE node (ops.BnPairFn) -- the shortcut's normalised tensor and the
+        # residual gradient are never written; PYLC_RUNTIME=fuse_proj_bn=0: the two BatchNorm nodes (A/B knob and the tests' reference)
+        self.fuse_proj_bn = True
         # the bias of a conv whose output a training-mode BatchNorm reads has an exactly zero gradient: no column-sum pass over dy for it
         self.skip_zero_bias_grad = True
         # precision mode 3: a BatchNorm whose only consumer is a depthwise conv leaves its apply pass to that conv's kernels (ops.bn_act(defer=))
