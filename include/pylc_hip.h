@@ -804,6 +804,37 @@ int pylc_region_sizes(const int* labels, long long N, int* sizes, void* stream);
 int pylc_sieve_regions(const unsigned char* mask, const int* labels, const int* sizes, int H, int W, int min_size, int ignore_index,
                        int fill, unsigned long long* best_ws, unsigned char* out, long long* n_changed, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Distance to the nearest pixel of another class, and scores along class borders: boundary IoU and trimap counts
+ * (csrc/boundary.hip; not in the reference).  Masks: uint8 [B][H][W], any values, contiguous, any byte
+ * address, 1 <= B*H*W < 2^31; every image of the batch on its own.  radius R in 1..254; ignore_index 0..255, or -1 for none.
+ *   d2(p) = min(R*R + 1, min |p - q|^2 over the pixels q of p's image with mask[q] != mask[p])     (squared Euclidean, saturated)
+ * A pixel equal to ignore_index differs from every class (it is a q for all of them) and gets -1 itself.  Only real pixels
+ * are q: the image edge is no border.  A labelled pixel lies in its mask's BAND when d2 <= R*R.  All integer, canonical.
+ * ------------------------------------------------------------------------------------------- */
+/* Bytes of device workspace (4-B aligned) the two entry points below need for such a batch; 0 for a shape out of range. */
+size_t pylc_boundary_workspace_bytes(int B, int H, int W);
+/* d2_out: int32 [B][H][W] (4-B aligned).  ignore_from: NULL, or a second mask of the same shape whose pixels equal to
+ * ignore_index count as ignored in `mask` too (needs an ignore_index).  Two launches (column pass, row pass), no host
+ * synchronisation.  A NULL mask / d2_out / workspace, a shape, radius or ignore_index out of range, ignore_from without an
+ * ignore_index: PYLC_ERR_ARG, nothing is launched. */
+int pylc_boundary_distance(const unsigned char* mask, int B, int H, int W, int radius, int ignore_index, const unsigned char* ignore_from,
+                           int* d2_out, void* workspace, void* stream);
+/* The band counts of a (truth, prediction) pair, ADDED into counts, int64 [C*C + 3C + 1] (8-B aligned; the caller zeroes it
+ * once and may launch many times into it): cm_band[t*C + p] over the pixels in the truth's band, then per class inter[c]
+ * (truth = pred = c, in both bands), gband[c] (truth = c, in the truth's band), pband[c] (pred = c, in the prediction's band),
+ * then one cell for pixels whose truth or prediction lies outside 0..C-1 without being the ignore label (tallied there and
+ * nowhere else).  Where the truth is ignored the prediction counts as ignored before its distances are taken, and only
+ * pixels with a labelled truth are counted; a prediction EQUAL to the ignore label at such a pixel enters gband only.
+ * Three launches and a 4-byte zero fill (two column passes, one fused row pass that counts instead of writing d2 maps).  n_classes 1..255 (above
+ * 32 a block counts with global instead of LDS atomics).  Argument errors as above: PYLC_ERR_ARG, nothing is launched. */
+int pylc_boundary_counts(const unsigned char* truth, const unsigned char* pred, int B, int H, int W, int n_classes, int radius,
+                         int ignore_index, unsigned long long* counts, void* workspace, void* stream);
+/* The same counts from two d2 maps already written: d2_truth = pylc_boundary_distance(truth), d2_pred =
+ * pylc_boundary_distance(pred, ignore_from = truth), N = B*H*W pixels.  One launch. */
+int pylc_boundary_counts_maps(const unsigned char* truth, const unsigned char* pred, const int* d2_truth, const int* d2_pred, long long N,
+                              int n_classes, int radius, int ignore_index, unsigned long long* counts, void* stream);
+
 /* The general form: ((x - mean[c]) / std[c]) / denom on float (is_u8 = 0) or uint8 (is_u8 = 1) tiles.  denom = 255 is
  * pylc_image_pack[_u8]; denom = 1 is the reference's grayscale `default=True` branch, which omits the division by 255
  * (models/model.py:428-430). */

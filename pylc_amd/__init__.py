@@ -10,3 +10,4 @@ from .runtime import runtime  # noqa: F401
 from .nets import DeepLab, UNet  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.pylc_hip.*)
 from . import regions  # noqa: F401  (connected regions and the small-region sieve of class masks)
+from . import boundary  # noqa: F401  (distance to the nearest other class; boundary IoU and trimap scores)

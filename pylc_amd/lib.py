@@ -217,6 +217,10 @@ SIGNATURES = {
     'pylc_label_regions': (_I, [_P, _I, _I, _I, _I, _P, _P]),
     'pylc_region_sizes': (_I, [_P, _LL, _P, _P]),
     'pylc_sieve_regions': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'pylc_boundary_workspace_bytes': (_SZ, [_I, _I, _I]),
+    'pylc_boundary_distance': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'pylc_boundary_counts': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'pylc_boundary_counts_maps': (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _P, _P]),
     'pylc_nhwc_to_nchw': (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     'pylc_nchw_to_nhwc': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'pylc_multiloss_workspace_floats': (_SZ, [_LL, _I]),

@@ -108,9 +108,18 @@ class ScoreLog:
     """Validation scores next to the loss log: add() accumulates the confusion counts of every validation batch on the device (one launch,
     no host read), close() turns them into one row per validation pass -- the only D2H copy -- and tracks the best weighted IoU."""
 
-    def __init__(self, n_classes, ignore_index=None):
+    def __init__(self, n_classes, ignore_index=None, boundary_radius=None):
         self.n_classes = int(n_classes)
         self.ignore_index = None if ignore_index is None else int(ignore_index)      # targets equal to it are dropped and reported as 'ignored'
+        # with a radius, add() also counts the band along class borders (boundary.boundary_counts on the mask of the same launch) and the
+        # rows gain 'boundary_iou', 'trimap_iou' and 'class_boundary_iou' (DESIGN.md 5.14); without one nothing changes
+        self.boundary_radius = None
+        if boundary_radius is not None:
+            from . import boundary
+            self.boundary_radius = boundary._check_radius(boundary_radius)
+            boundary._check_classes(self.n_classes)
+            boundary._check_ignore(self.ignore_index)
+        self.boundary_counts = None        # int64 [C*C + 3C + 1], allocated with `counts`
         self.counts = None                 # int64 [C*C + 1] (+ 1 with an ignore label), allocated where the first logits live
         self.last_counts = None            # host int64 [C,C] of the last closed pass (summed over the group)
         self.rows = []
@@ -124,19 +133,38 @@ class ScoreLog:
             raise ValueError('ScoreLog of %d classes got logits with %d' % (self.n_classes, logits.shape[1]))
         if self.counts is None:
             self.counts = self._zeros(logits.device)
-        logits_confusion(logits, target, counts=self.counts, ignore_index=self.ignore_index)
+        if self.boundary_radius is None:
+            logits_confusion(logits, target, counts=self.counts, ignore_index=self.ignore_index)
+            return
+        from . import boundary
+        _, mask = logits_confusion(logits, target, counts=self.counts, return_mask=True, ignore_index=self.ignore_index)
+        if self.boundary_counts is None:
+            self.boundary_counts = torch.zeros(boundary.n_cells(self.n_classes), device=mask.device, dtype=torch.int64)
+        # (a target outside 0..255 wraps here; the launch above has counted it in the out-of-range cell, which close() raises on)
+        truth = target.to(mask.device, non_blocking=True).reshape(mask.shape).to(torch.uint8)
+        boundary.boundary_counts(truth, mask, self.n_classes, self.boundary_radius, self.ignore_index, counts=self.boundary_counts)
 
     def close(self, it, epoch, group=None):
         """End of a validation pass: the counts (summed over `group` when given -- a collective every rank must reach) become a row
         {'iter', 'epoch', 'f1', 'iou', 'mcc', 'class_iou', 'class_f1', 'support'} (with an ignore label also 'ignored', the number of
-        dropped pixels); the device counts are zeroed for the next pass.  Returns the row, or None when no valid pixel was added."""
+        dropped pixels; with a boundary radius also 'boundary_iou', 'trimap_iou', 'class_boundary_iou'); the device counts are zeroed
+        for the next pass.  Returns the row, or None when no valid pixel was added."""
         c = self.n_classes
         if self.counts is None:
             self.counts = self._zeros('cpu')           # a rank that saw no batch still takes part in the collective
         if group is not None:
             from .runtime import runtime
             runtime.sync_all_reduce(self.counts, group)           # int64: carried by the torch group (the native communicator takes floats)
-        host = self.counts.to('cpu', copy=True)                    # the one D2H copy of a validation pass
+        bhost = None
+        if self.boundary_radius is not None:
+            from . import boundary
+            if self.boundary_counts is None:
+                self.boundary_counts = torch.zeros(boundary.n_cells(c), device=self.counts.device, dtype=torch.int64)
+            if group is not None:
+                runtime.sync_all_reduce(self.boundary_counts, group)
+            bhost = self.boundary_counts.to('cpu', copy=True)
+            self.boundary_counts.zero_()
+        host = self.counts.to('cpu', copy=True)                    # the one D2H copy of a validation pass (two with a boundary radius)
         self.counts.zero_()
         outside = int(host[c * c])
         if outside:
@@ -151,6 +179,9 @@ class ScoreLog:
                'class_iou': [float(v) for v in pc['iou']], 'class_f1': [float(v) for v in pc['f1']], 'support': [int(v) for v in pc['support']]}
         if self.ignore_index is not None:
             row['ignored'] = int(host[c * c + 1])
+        if bhost is not None:
+            b = boundary.boundary_scores(bhost, c)
+            row.update(boundary_iou=b['boundary_iou'], trimap_iou=b['trimap_iou'], class_boundary_iou=[float(v) for v in b['class_boundary_iou']])
         self.rows.append(row)
         self.is_best = row['iou'] > self.best_iou
         if self.is_best:

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import metrics, ops, regions, lib as L
+from . import boundary, metrics, ops, regions, lib as L
 from .inference import gather_tiles, predict_blend_mean, predict_overlap_tile, shard_batches, tile_grid
 from .lib import lib, check, ptr, stream
 
@@ -319,9 +319,13 @@ class PhotoEvaluator:
     """The reference's Evaluator over segment_photo results, counts on the device (one int64 [C, C] matrix; nothing pixel-sized reaches the
     host).  add() scores one image as Evaluator.evaluate() does (validate() overwrites the first C pixels: force_coverage);
     aggregate() is the --aggregate_metrics result, where validate() overwrites the first C pixels of the CONCATENATION only
-    (utils/evaluate.py:150-176): the first image's counts with that coverage, every later image's without."""
+    (utils/evaluate.py:150-176): the first image's counts with that coverage, every later image's without.
 
-    def __init__(self, n_classes, palette, ignore_index=None):
+    boundary_radius (an int, or 'auto' for boundary.default_radius of each image's scaled size): add() also accumulates the image's band
+    counts (boundary.boundary_counts; no coverage overwrite applies to them), and add() / aggregate() return
+    boundary.boundary_scores' keys next to the four above.  None (default): nothing changes."""
+
+    def __init__(self, n_classes, palette, ignore_index=None, boundary_radius=None):
         self.n_classes = int(n_classes)
         # with an ignore label (0..255) a ground-truth colour outside the palette is encoded as it, and only the other pixels are scored
         self.ignore_index = None if ignore_index is None else int(ignore_index)
@@ -330,6 +334,12 @@ class PhotoEvaluator:
             raise ValueError('palette has %d entries for %d classes' % (self.palette.shape[0], self.n_classes))
         self.cm = None
         self.count = 0
+        if boundary_radius is not None and boundary_radius != 'auto':
+            boundary_radius = boundary._check_radius(boundary_radius)
+        if boundary_radius is not None:
+            boundary._check_ignore(self.ignore_index)
+        self.boundary_radius = boundary_radius
+        self.boundary_counts = None        # int64 [C*C + 3C + 1] over the images added so far
 
     def add(self, result, gt_rgb):
         """Encode the ground-truth RGB mask ([H,W,3] uint8, full size) at the result's scaled size (get_image(scale, INTER_NEAREST)) and
@@ -347,11 +357,18 @@ class PhotoEvaluator:
             raise ValueError('predicted mask %s vs ground truth %s' % (tuple(y_pred.shape), tuple(y_true.shape)))
         cm = metrics.confusion_matrix(y_true, y_pred, self.n_classes, force_coverage=True, ignore_index=ign)
         plain = None if self.cm is None else metrics.confusion_matrix(y_true, y_pred, self.n_classes, force_coverage=False, ignore_index=ign)
-        return self.add_counts(cm, plain)
+        band = None
+        if self.boundary_radius is not None:
+            r = boundary.default_radius(h_s, w_s) if self.boundary_radius == 'auto' else self.boundary_radius
+            band = boundary.boundary_counts(y_true, y_pred, self.n_classes, r, ign)
+        return self.add_counts(cm, plain, band)
 
-    def add_counts(self, cm_coverage, cm_plain=None):
+    def add_counts(self, cm_coverage, cm_plain=None, boundary_counts=None):
         """Accumulate one image given its count matrices with and without the coverage overwrite (device tensors, or host arrays for
-        counts made elsewhere); cm_plain is needed from the second image on.  Returns the image's scores (those of cm_coverage)."""
+        counts made elsewhere); cm_plain is needed from the second image on.  boundary_counts: the image's band counts, needed exactly
+        when the evaluator has a boundary radius.  Returns the image's scores (those of cm_coverage, and of its own band counts)."""
+        if (boundary_counts is None) != (self.boundary_radius is None):
+            raise ValueError('add_counts: band counts are given exactly when the evaluator has a boundary_radius')
         if self.cm is None:
             self.cm = cm_coverage.clone() if torch.is_tensor(cm_coverage) else np.array(cm_coverage, dtype=np.int64)
         else:
@@ -359,9 +376,19 @@ class PhotoEvaluator:
                 raise ValueError('add_counts: every image after the first needs its counts without coverage')
             self.cm += cm_plain
         self.count += 1
-        return metrics.scores(cm_coverage)
+        out = metrics.scores(cm_coverage)
+        if boundary_counts is not None:
+            if self.boundary_counts is None:
+                self.boundary_counts = boundary_counts.clone() if torch.is_tensor(boundary_counts) else np.array(boundary_counts, dtype=np.int64)
+            else:
+                self.boundary_counts += boundary_counts
+            out.update(boundary.boundary_scores(boundary_counts, self.n_classes))
+        return out
 
     def aggregate(self):
         if self.cm is None:
             raise ValueError('aggregate evaluation: no images added')
-        return metrics.scores(self.cm)
+        out = metrics.scores(self.cm)
+        if self.boundary_counts is not None:
+            out.update(boundary.boundary_scores(self.boundary_counts, self.n_classes))
+        return out

@@ -31,13 +31,16 @@ def validate(model, batches, save_dir=None):
     return model
 
 
-def trainer(model, train_batches, valid_batches, n_epochs, save_dir=None, score=False, best_by='dice'):
+def trainer(model, train_batches, valid_batches, n_epochs, save_dir=None, score=False, best_by='dice', boundary_radius=None):
     """train.py:72-92, including its resume quirk `range(offset, n_epochs - offset)`.
     score: every validation pass also logs weighted F1 / IoU / MCC and the per-class scores (metrics.ScoreLog -> scores.json next to
-    losses.pth); best_by: 'dice' (the reference's rule) or 'iou' (needs score) picks what the best-model copy follows."""
+    losses.pth); best_by: 'dice' (the reference's rule) or 'iou' (needs score) picks what the best-model copy follows.
+    boundary_radius (needs score): the rows also carry boundary IoU and the trimap IoU of the band of that many pixels."""
+    if boundary_radius is not None and not score:
+        raise ValueError('boundary_radius needs score=True')
     if score and model.scores is None:
         from .metrics import ScoreLog
-        model.scores = ScoreLog(model.meta.n_classes, getattr(model.meta, 'ignore_index', None))
+        model.scores = ScoreLog(model.meta.n_classes, getattr(model.meta, 'ignore_index', None), boundary_radius=boundary_radius)
     model.best_by = best_by
     model.net.train()
     offset = model.epoch
