@@ -599,8 +599,10 @@ int pylc_image_pack(const float* img_nchw, int B, int Cimg, int H, int W, const 
  * reconstruct() (overlap quirks reproduced, see csrc/stitch.hip); palette + INTER_NEAREST resize replacing
  * colourize utils/tools.py:322-358 and the cv2.resize at :315-317.
  * ------------------------------------------------------------------------------------------- */
-/* img: [Cimg][H][W] raw 0..255 (fitted: H, W multiples of stride); writes tiles first_tile .. first_tile+n_tiles-1
- * (row-major tile order) as normalised [n][tile][tile][4]. mean3/std3 are HOST arrays. */
+/* img: [Cimg][H][W] raw 0..255; writes tiles first_tile .. first_tile+n_tiles-1 (row-major tile order) of the fitted grid
+ * rows = (H - tile) / stride + 1, cols = (W - tile) / stride + 1 (a remainder right and below is dropped) as normalised
+ * [n][tile][tile][4]. mean3/std3 are HOST arrays.  Its own checks, then the shared cutter (csrc/pack_tiles.hip: one kernel
+ * behind the five pylc_image_pack_tiles* entry points; this grid is its case out = tile, pad = 0). */
 int pylc_image_pack_tiles(const float* img, int Cimg, int H, int W, int tile, int stride, int first_tile, int n_tiles,
                           const float* mean3, const float* std3, float* out, void* stream);
 /* logits: [rows*cols][tile][tile][pitch] (NHWC tiles in row-major order), stride = tile or tile/2.
@@ -620,7 +622,8 @@ int pylc_colourize_resize(const unsigned char* mask, int h, int w, const unsigne
  * ------------------------------------------------------------------------------------------- */
 /* img: [Cimg][H][W] raw 0..255, float32 (is_u8 = 0) or uint8 (is_u8 = 1), any H, W meeting the above; writes tiles
  * first_tile .. first_tile+n_tiles-1 (row-major tile order) as [n][tile][tile][4] with pylc_image_pack_tiles'
- * arithmetic, ((v - mean) / std) / 255, channel 3 = 0, one image channel copied into three.  mean3/std3: HOST arrays. */
+ * arithmetic, ((v - mean) / std) / 255, channel 3 = 0, one image channel copied into three.  mean3/std3: HOST arrays.
+ * Its own checks (tile > out: pad >= 1), then the shared cutter (csrc/pack_tiles.hip). */
 int pylc_image_pack_tiles_reflect(const void* img, int is_u8, int Cimg, int H, int W, int tile, int out, int stride,
                                   int first_tile, int n_tiles, const float* mean3, const float* std3, float* tiles,
                                   void* stream);
@@ -654,7 +657,7 @@ int pylc_class_encode_resize(const unsigned char* rgb, int H, int W, const unsig
 int pylc_class_encode_resize_ex(const unsigned char* rgb, int H, int W, const unsigned char* palette_rgb, int n_classes,
                                 unsigned char* out, int oh, int ow, int unmatched_value, void* stream);
 /* pylc_image_pack_tiles on a float32 (is_u8 = 0) or uint8 (is_u8 = 1) image [Cimg][H][W]: same arguments and arithmetic,
- * bit-identical tiles for equal pixel values (csrc/stitch.hip). */
+ * bit-identical tiles for equal pixel values.  Its own checks, then the shared cutter (csrc/pack_tiles.hip). */
 int pylc_image_pack_tiles_ex(const void* img, int is_u8, int Cimg, int H, int W, int tile, int stride, int first_tile,
                              int n_tiles, const float* mean3, const float* std3, float* out, void* stream);
 
@@ -678,11 +681,13 @@ int pylc_blend_accumulate(const float* logits, int pitch, int first_tile, int n_
 int pylc_blend_finalize(const float* acc, int acc_pitch, int H, int W, int out, int stride, int C, int members,
                         unsigned char* mask, float* probs, float* conf, void* stream);
 /* pylc_image_pack_tiles_ex with a trailing flip: flip = 1 writes every window mirrored along x (output column c0 reads source
- * column x0 + tile - 1 - c0); flip = 0 gives pylc_image_pack_tiles_ex's bytes. */
+ * column x0 + tile - 1 - c0); flip = 0 gives pylc_image_pack_tiles_ex's bytes.  Its own checks, then the shared cutter
+ * (csrc/pack_tiles.hip). */
 int pylc_image_pack_tiles_flip(const void* img, int is_u8, int Cimg, int H, int W, int tile, int stride, int first_tile,
                                int n_tiles, const float* mean3, const float* std3, float* out, void* stream, int flip);
 /* pylc_image_pack_tiles_reflect with the same trailing flip, and with tile == out (pad = 0) accepted: a same-size network on
- * the any-size grid. */
+ * the any-size grid (on a fitted image that grid is pylc_image_pack_tiles_ex's, tile for tile).  Its own checks, then the
+ * shared cutter (csrc/pack_tiles.hip). */
 int pylc_image_pack_tiles_reflect_ex(const void* img, int is_u8, int Cimg, int H, int W, int tile, int out, int stride,
                                      int first_tile, int n_tiles, const float* mean3, const float* std3, float* tiles,
                                      void* stream, int flip);

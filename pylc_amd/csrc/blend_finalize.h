@@ -67,13 +67,4 @@ __global__ __launch_bounds__(256) void blend_finalize_kernel(const float* __rest
 
 }  // namespace
 
-#define PYLC_BLEND_SWITCH(C, LAUNCH, who)                                                                                              \
-    switch (C) {                                                                                                                       \
-        case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; case 4: LAUNCH(4); break; case 5: LAUNCH(5); break;                        \
-        case 6: LAUNCH(6); break; case 7: LAUNCH(7); break; case 8: LAUNCH(8); break; case 9: LAUNCH(9); break;                        \
-        case 10: LAUNCH(10); break; case 11: LAUNCH(11); break; case 12: LAUNCH(12); break; case 13: LAUNCH(13); break;                \
-        case 14: LAUNCH(14); break; case 15: LAUNCH(15); break; case 16: LAUNCH(16); break;                                            \
-        default: return fail(PYLC_ERR_ARG, who ": n_classes=%d unsupported (2..%d)", C, PYLC_MAX_CLASSES);                             \
-    }
-
 }  // namespace pylc

@@ -32,6 +32,17 @@ inline int fail(int code, const char* fmt, ...) {
 
 #define PYLC_LAUNCH_CHECK() PYLC_HIP(hipGetLastError())
 
+// The one dispatch over the class counts 2..PYLC_MAX_CLASSES that are template parameters: LAUNCH(CC) with the compile-time count CC == C,
+// or the caller returns PYLC_ERR_ARG in the name `who` (a string literal).
+#define PYLC_FOR_CLASSES(C, LAUNCH, who)                                                                                               \
+    switch (C) {                                                                                                                       \
+        case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; case 4: LAUNCH(4); break; case 5: LAUNCH(5); break;                        \
+        case 6: LAUNCH(6); break; case 7: LAUNCH(7); break; case 8: LAUNCH(8); break; case 9: LAUNCH(9); break;                        \
+        case 10: LAUNCH(10); break; case 11: LAUNCH(11); break; case 12: LAUNCH(12); break; case 13: LAUNCH(13); break;                \
+        case 14: LAUNCH(14); break; case 15: LAUNCH(15); break; case 16: LAUNCH(16); break;                                            \
+        default: return ::pylc::fail(PYLC_ERR_ARG, who ": n_classes=%d unsupported (2..%d)", C, PYLC_MAX_CLASSES);                     \
+    }
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 template <typename T>

@@ -201,15 +201,6 @@ __global__ __launch_bounds__(256) void multiloss_bwd_kernel(const float* __restr
     if (amax_out != nullptr) amax_commit(gmax, amax_out);
 }
 
-#define PYLC_FOR_C(MACRO)                                                                                              \
-    switch (C) {                                                                                                       \
-        case 2: MACRO(2); break; case 3: MACRO(3); break; case 4: MACRO(4); break; case 5: MACRO(5); break;           \
-        case 6: MACRO(6); break; case 7: MACRO(7); break; case 8: MACRO(8); break; case 9: MACRO(9); break;           \
-        case 10: MACRO(10); break; case 11: MACRO(11); break; case 12: MACRO(12); break; case 13: MACRO(13); break;   \
-        case 14: MACRO(14); break; case 15: MACRO(15); break; case 16: MACRO(16); break;                              \
-        default: return fail(PYLC_ERR_ARG, "multiloss: n_classes=%d unsupported (2..%d)", C, MAXC);                   \
-    }
-
 }  // namespace pylc
 
 using namespace pylc;
@@ -228,15 +219,15 @@ static int multiloss_stats_impl(const float* logits, int pitch, const void* targ
                        workspace, ignore, n_bad)
     if (!ign) {
 #define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, false)
-        PYLC_FOR_C(LAUNCH_STATS)
+        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
 #undef LAUNCH_STATS
     } else if (target_bytes == 8) {
 #define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, true)
-        PYLC_FOR_C(LAUNCH_STATS)
+        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
 #undef LAUNCH_STATS
     } else {
 #define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, unsigned char, true)
-        PYLC_FOR_C(LAUNCH_STATS)
+        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
 #undef LAUNCH_STATS
     }
 #undef LAUNCH_STATS_T
@@ -297,15 +288,15 @@ static int multiloss_bwd_impl(const float* logits, int pitch, const void* target
                        stats, inv_n, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, Cstore, amax_bits, ignore, zero16)
     if (!ign) {
 #define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, false)
-        PYLC_FOR_C(LAUNCH_BWD)
+        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
 #undef LAUNCH_BWD
     } else if (target_bytes == 8) {
 #define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, true)
-        PYLC_FOR_C(LAUNCH_BWD)
+        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
 #undef LAUNCH_BWD
     } else {
 #define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, unsigned char, true)
-        PYLC_FOR_C(LAUNCH_BWD)
+        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
 #undef LAUNCH_BWD
     }
 #undef LAUNCH_BWD_T

@@ -157,7 +157,7 @@ extern "C" int pylc_blend_resample_accumulate(const float* acc_s, int src_pitch,
     const int blocks = ot_grid((long long)H * W);
     hipStream_t st = as_stream(stream);
 #define LAUNCH_RS(CC) hipLaunchKernelGGL((blend_resample_kernel<CC>), dim3(blocks), dim3(256), 0, st, acc_s, g, ens)
-    PYLC_BLEND_SWITCH(C, LAUNCH_RS, "blend_resample_accumulate")
+    PYLC_FOR_CLASSES(C, LAUNCH_RS, "blend_resample_accumulate")
 #undef LAUNCH_RS
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
@@ -175,7 +175,7 @@ extern "C" int pylc_ensemble_finalize(const float* ens, int pitch, int H, int W,
     const int blocks = ot_grid(cdiv<long long>((long long)H * W, kOtPx));
     hipStream_t st = as_stream(stream);
 #define LAUNCH_EF(CC) hipLaunchKernelGGL((blend_finalize_kernel<CC, false>), dim3(blocks), dim3(256), 0, st, ens, g, 1, total_weight, mask, probs, conf)
-    PYLC_BLEND_SWITCH(C, LAUNCH_EF, "ensemble_finalize")
+    PYLC_FOR_CLASSES(C, LAUNCH_EF, "ensemble_finalize")
 #undef LAUNCH_EF
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;

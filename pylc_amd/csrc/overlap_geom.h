@@ -1,4 +1,5 @@
-// The overlap-tile geometry shared by csrc/overlap_tile.hip (the one-shot blend) and csrc/blend.hip (the streaming blend):
+// The overlap-tile geometry shared by csrc/pack_tiles.hip (the tile cutter), csrc/overlap_tile.hip (the one-shot blend) and
+// csrc/blend.hip (the streaming blend):
 //
 //   output-tile origins along an axis of length n:  o_i = min(i*stride, n - out),  i = 0 .. ceil((n - out) / stride), tiles in
 //   row-major order; 1 <= stride <= out <= n.  A fitted image, (n - out) % stride == 0, is the case in which the clamp is never active.
@@ -30,6 +31,28 @@ __device__ __forceinline__ Cover overlap_cover(int y, int n, int out, int stride
     c.hi = h < cnt - 2 ? h : cnt - 2;
     c.last = y >= n - out ? 1 : 0;
     return c;
+}
+
+// acc[c] += softmax(v)[c] for the C logits that start at the 16-byte aligned `src` (pitch >= C rounded up to 4): the per-tile term of the
+// mean-probability blend, stated once so that the one-shot and the streaming blend add the same bits in the same order.
+template <int C, int N>
+__device__ __forceinline__ void softmax_add(const ot_f32x4* __restrict__ src, float (&acc)[N]) {
+    constexpr int NV = (C + 3) / 4;
+    float v[NV * 4];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const ot_f32x4 t = src[k];
+        v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w;
+    }
+    float m = v[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) { v[c] = expf(v[c] - m); s += v[c]; }
+    const float inv = 1.f / s;
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] += v[c] * inv;
 }
 
 __device__ __forceinline__ int reflect101(int y, int n) {

@@ -10,50 +10,17 @@
 //   score of an image pixel = mean of the softmax probabilities of every tile that covers it (equal weights, summed in tile order:
 //   rows ascending, then columns -- no atomics, deterministic); class = argmax, first maximum
 //
-// pack_tiles_reflect_kernel cuts and normalises the windows straight from the device image (float or uint8); stitch_overlap_kernel
+// pack_tiles.hip's cutter cuts and normalises the windows straight from the device image (float or uint8); stitch_overlap_kernel here
 // reads each pixel's covering logit tiles (<= ceil(out/stride)+1 per axis) and writes the uint8 mask, optionally the mean
 // probabilities [C][H][W] (the reference's mask_fullsized layout).
-#include <type_traits>
-
 #include "common.h"
-#include "overlap_geom.h"      // the geometry: overlap_count, overlap_origin, overlap_cover, reflect101, overlap_check
+#include "overlap_geom.h"      // the geometry: overlap_count, overlap_origin, overlap_cover, overlap_check; softmax_add
 
 namespace pylc {
 
 namespace {
 
 struct OverlapGeom { int H, W, out, stride, rows, cols, pitch; };
-
-// tiles [count][tile][tile][4] <- normalised mirrored windows of img [Cimg][H][W] (raw 0..255), tiles first .. first+count-1 in
-// row-major tile order.  pack_tiles_kernel's arithmetic, ((v - m) / s) / 255, channel 3 = 0; one channel is copied into three.
-template <bool U8>
-__global__ __launch_bounds__(256) void pack_tiles_reflect_kernel(const void* __restrict__ img_, int Cimg, int H, int W, int tile, int out,
-                                                                  int stride, int cols, int first, int count, float m0, float m1, float m2,
-                                                                  float s0, float s1, float s2, float* __restrict__ tiles) {
-    typedef typename std::conditional<U8, unsigned char, float>::type T;
-    const T* __restrict__ img = static_cast<const T*>(img_);
-    const int pad = (tile - out) / 2;
-    const long long total = (long long)count * tile * tile;
-    const size_t plane = (size_t)H * W;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c0 = (int)(i % tile);
-        const long long t = i / tile;
-        const int r = (int)(t % tile);
-        const int k = first + (int)(t / tile);
-        const int y = reflect101(overlap_origin(k / cols, H, out, stride) - pad + r, H);
-        const int x = reflect101(overlap_origin(k % cols, W, out, stride) - pad + c0, W);
-        const T* src = img + (size_t)y * W + x;
-        const float a = (float)src[0];
-        const float b = Cimg == 3 ? (float)src[plane] : a;
-        const float c = Cimg == 3 ? (float)src[2 * plane] : a;
-        ot_f32x4 v;
-        v.x = ((a - m0) / s0) / 255.f;
-        v.y = ((b - m1) / s1) / 255.f;
-        v.z = ((c - m2) / s2) / 255.f;
-        v.w = 0.f;
-        *reinterpret_cast<ot_f32x4*>(tiles + 4 * i) = v;
-    }
-}
 
 // logits [rows*cols][out][out][pitch] (NHWC tiles, row-major tile order) -> mask [H][W] (uint8), probs [C][H][W] (fp32, optional).
 // Lane q owns the linear pixels 4q .. 4q+3 (they may straddle a row or a tile edge: every pixel finds its own covering tiles); the
@@ -62,7 +29,6 @@ __global__ __launch_bounds__(256) void pack_tiles_reflect_kernel(const void* __r
 template <int C>
 __global__ __launch_bounds__(256) void stitch_overlap_kernel(const float* __restrict__ logits, OverlapGeom g, unsigned char* __restrict__ mask,
                                                               float* __restrict__ probs) {
-    constexpr int NV = (C + 3) / 4;
     const long long total = (long long)g.H * g.W;
     const long long groups = cdiv<long long>(total, kOtPx);
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += (long long)gridDim.x * blockDim.x) {
@@ -87,21 +53,7 @@ __global__ __launch_bounds__(256) void stitch_overlap_kernel(const float* __rest
                     const int lx = x - overlap_origin(tj, g.W, g.out, g.stride);
                     const ot_f32x4* src = reinterpret_cast<const ot_f32x4*>(
                         logits + (((size_t)(ti * g.cols + tj) * g.out + ly) * g.out + lx) * g.pitch);
-                    float v[NV * 4];
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) {
-                        const ot_f32x4 t = src[k];
-                        v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w;
-                    }
-                    float m = v[0];
-#pragma unroll
-                    for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
-                    float s = 0.f;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) { v[c] = expf(v[c] - m); s += v[c]; }
-                    const float inv = 1.f / s;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) acc[c] += v[c] * inv;
+                    softmax_add<C>(src, acc);
                     ++n;
                 }
             }
@@ -132,26 +84,6 @@ __global__ __launch_bounds__(256) void stitch_overlap_kernel(const float* __rest
 
 using namespace pylc;
 
-extern "C" int pylc_image_pack_tiles_reflect(const void* img, int is_u8, int Cimg, int H, int W, int tile, int out, int stride, int first_tile,
-                                             int n_tiles, const float* mean3, const float* std3, float* tiles, void* stream) {
-    PYLC_REQUIRE(img && tiles && mean3 && std3 && (Cimg == 1 || Cimg == 3) && tile > out && (tile - out) % 2 == 0,
-                 "image_pack_tiles_reflect: bad arguments");
-    if (int rc = overlap_check("image_pack_tiles_reflect", H, W, out, stride, (tile - out) / 2)) return rc;
-    const int rows = overlap_count(H, out, stride), cols = overlap_count(W, out, stride);
-    PYLC_REQUIRE(first_tile >= 0 && n_tiles > 0 && (long long)first_tile + n_tiles <= (long long)rows * cols,
-                 "image_pack_tiles_reflect: tiles %d..%d outside the %dx%d grid", first_tile, first_tile + n_tiles - 1, rows, cols);
-    const long long total = (long long)n_tiles * tile * tile;
-    hipStream_t st = as_stream(stream);
-    if (is_u8)
-        hipLaunchKernelGGL(pack_tiles_reflect_kernel<true>, dim3(ot_grid(total)), dim3(256), 0, st, img, Cimg, H, W, tile, out, stride, cols,
-                           first_tile, n_tiles, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], tiles);
-    else
-        hipLaunchKernelGGL(pack_tiles_reflect_kernel<false>, dim3(ot_grid(total)), dim3(256), 0, st, img, Cimg, H, W, tile, out, stride, cols,
-                           first_tile, n_tiles, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], tiles);
-    PYLC_LAUNCH_CHECK();
-    return PYLC_OK;
-}
-
 extern "C" int pylc_stitch_overlap_argmax(const float* logits, int pitch, int n_tiles, int H, int W, int out, int stride, int C,
                                           unsigned char* mask, float* probs, void* stream) {
     PYLC_REQUIRE(logits && mask && pitch >= C && pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0,
@@ -164,13 +96,7 @@ extern "C" int pylc_stitch_overlap_argmax(const float* logits, int pitch, int n_
     const int blocks = ot_grid(cdiv<long long>((long long)H * W, kOtPx));
     hipStream_t st = as_stream(stream);
 #define LAUNCH_OT(CC) hipLaunchKernelGGL((stitch_overlap_kernel<CC>), dim3(blocks), dim3(256), 0, st, logits, g, mask, probs)
-    switch (C) {
-        case 2: LAUNCH_OT(2); break; case 3: LAUNCH_OT(3); break; case 4: LAUNCH_OT(4); break; case 5: LAUNCH_OT(5); break;
-        case 6: LAUNCH_OT(6); break; case 7: LAUNCH_OT(7); break; case 8: LAUNCH_OT(8); break; case 9: LAUNCH_OT(9); break;
-        case 10: LAUNCH_OT(10); break; case 11: LAUNCH_OT(11); break; case 12: LAUNCH_OT(12); break; case 13: LAUNCH_OT(13); break;
-        case 14: LAUNCH_OT(14); break; case 15: LAUNCH_OT(15); break; case 16: LAUNCH_OT(16); break;
-        default: return fail(PYLC_ERR_ARG, "stitch_overlap_argmax: n_classes=%d unsupported (2..%d)", C, PYLC_MAX_CLASSES);
-    }
+    PYLC_FOR_CLASSES(C, LAUNCH_OT, "stitch_overlap_argmax")
 #undef LAUNCH_OT
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;

@@ -170,15 +170,6 @@ static void score_launch(bool vec, int blocks, hipStream_t st, const float* logi
                            N, off, mask, counts, has_ign, ign);
 }
 
-#define PYLC_SCORE_FOR_C(MACRO)                                                                                        \
-    switch (C) {                                                                                                       \
-        case 2: MACRO(2); break; case 3: MACRO(3); break; case 4: MACRO(4); break; case 5: MACRO(5); break;           \
-        case 6: MACRO(6); break; case 7: MACRO(7); break; case 8: MACRO(8); break; case 9: MACRO(9); break;           \
-        case 10: MACRO(10); break; case 11: MACRO(11); break; case 12: MACRO(12); break; case 13: MACRO(13); break;   \
-        case 14: MACRO(14); break; case 15: MACRO(15); break; case 16: MACRO(16); break;                              \
-        default: return fail(PYLC_ERR_ARG, "logits_score: n_classes=%d unsupported (2..%d)", C, SCORE_MAXC);          \
-    }
-
 }  // namespace pylc
 
 using namespace pylc;
@@ -204,15 +195,15 @@ static int logits_score_impl(const float* logits, int pitch, const void* target,
     hipStream_t st = as_stream(stream);
     if (!counts) {                                                                 // mask only: a target, if any, is not read
 #define LAUNCH_SC(CC) score_launch<CC, unsigned char, false>(vec, blocks, st, logits, pitch, nullptr, N, off, mask, nullptr, 0, 0)
-        PYLC_SCORE_FOR_C(LAUNCH_SC)
+        PYLC_FOR_CLASSES(C, LAUNCH_SC, "logits_score")
 #undef LAUNCH_SC
     } else if (target_bytes == 8) {
 #define LAUNCH_SC(CC) score_launch<CC, long long, true>(vec, blocks, st, logits, pitch, target, N, off, mask, counts, has_ign, ign)
-        PYLC_SCORE_FOR_C(LAUNCH_SC)
+        PYLC_FOR_CLASSES(C, LAUNCH_SC, "logits_score")
 #undef LAUNCH_SC
     } else {
 #define LAUNCH_SC(CC) score_launch<CC, unsigned char, true>(vec, blocks, st, logits, pitch, target, N, off, mask, counts, has_ign, ign)
-        PYLC_SCORE_FOR_C(LAUNCH_SC)
+        PYLC_FOR_CLASSES(C, LAUNCH_SC, "logits_score")
 #undef LAUNCH_SC
     }
     PYLC_LAUNCH_CHECK();
@@ -227,4 +218,85 @@ extern "C" int pylc_logits_score(const float* logits, int pitch, const void* tar
 extern "C" int pylc_logits_score_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
                                     int ignore_index, unsigned long long* counts, void* stream) {
     return logits_score_impl(logits, pitch, target, target_bytes, N, C, mask, counts, 1, (long long)ignore_index, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Evaluation: confusion matrix of class-index masks (replaces the sklearn passes over ~1e7-pixel flattened arrays in
+// utils/metrics.py:64-88; the scores are simple functions of the n_cls x n_cls count matrix).  Integer counts in LDS,
+// merged with 64-bit integer atomics: exact and order-independent.  Evaluator.validate()'s coverage quirk
+// (utils/evaluate.py:171-174: the first n_classes pixels of both arrays are overwritten with 0..n_classes-1) is applied
+// on the fly when force_coverage != 0.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace pylc {
+// IGN: pixels whose true label equals `ignore` (compared after widening) or lies outside 0..C-1 are left out of the matrix and counted in
+// skipped[1] / skipped[0].  Without IGN a pixel with either label out of range is dropped silently, as before.
+template <typename TT, typename TP, bool IGN>
+__global__ __launch_bounds__(256) void confusion_kernel(const TT* __restrict__ yt, const TP* __restrict__ yp, long long n, int C,
+                                                         int force_coverage, unsigned long long* __restrict__ cm, long long ignore,
+                                                         unsigned long long* __restrict__ skipped) {
+    __shared__ unsigned int hist[SCORE_MAXC * SCORE_MAXC + 2];
+    for (int i = threadIdx.x; i < C * C + 2; i += 256) hist[i] = 0;
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        if constexpr (IGN) {
+            long long tl = (long long)yt[i];
+            int p = (int)yp[i];
+            if (force_coverage && i < C) { tl = i; p = (int)i; }
+            if (tl == ignore) atomicAdd(&hist[C * C + 1], 1u);
+            else if ((unsigned long long)tl >= (unsigned long long)C) atomicAdd(&hist[C * C], 1u);
+            else if ((unsigned)p < (unsigned)C) atomicAdd(&hist[(int)tl * C + p], 1u);
+        } else {
+            int t = (int)yt[i], p = (int)yp[i];
+            if (force_coverage && i < C) { t = (int)i; p = (int)i; }
+            if ((unsigned)t < (unsigned)C && (unsigned)p < (unsigned)C) atomicAdd(&hist[t * C + p], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < C * C; i += 256)
+        if (hist[i]) atomicAdd(&cm[i], (unsigned long long)hist[i]);
+    if constexpr (IGN) {
+        if (skipped != nullptr && threadIdx.x < 2 && hist[C * C + threadIdx.x]) atomicAdd(&skipped[threadIdx.x], (unsigned long long)hist[C * C + threadIdx.x]);
+    }
+}
+
+template <bool IGN>
+static void confusion_launch(const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C, int force_coverage,
+                             unsigned long long* cm, long long ignore, unsigned long long* skipped, hipStream_t st) {
+    const long long want = cdiv<long long>(n, 256);
+    const int blocks = (int)(want < 1024 ? want : 1024);
+    if (true_bytes == 1 && pred_bytes == 1)
+        hipLaunchKernelGGL((confusion_kernel<unsigned char, unsigned char, IGN>), dim3(blocks), dim3(256), 0, st, (const unsigned char*)y_true,
+                           (const unsigned char*)y_pred, n, C, force_coverage, cm, ignore, skipped);
+    else if (true_bytes == 8 && pred_bytes == 1)
+        hipLaunchKernelGGL((confusion_kernel<long long, unsigned char, IGN>), dim3(blocks), dim3(256), 0, st, (const long long*)y_true,
+                           (const unsigned char*)y_pred, n, C, force_coverage, cm, ignore, skipped);
+    else if (true_bytes == 1 && pred_bytes == 8)
+        hipLaunchKernelGGL((confusion_kernel<unsigned char, long long, IGN>), dim3(blocks), dim3(256), 0, st, (const unsigned char*)y_true,
+                           (const long long*)y_pred, n, C, force_coverage, cm, ignore, skipped);
+    else
+        hipLaunchKernelGGL((confusion_kernel<long long, long long, IGN>), dim3(blocks), dim3(256), 0, st, (const long long*)y_true,
+                           (const long long*)y_pred, n, C, force_coverage, cm, ignore, skipped);
+}
+}  // namespace pylc
+
+template <bool IGN>
+static int confusion_impl(const char* who, const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C,
+                          int force_coverage, unsigned long long* cm, long long ignore, unsigned long long* skipped, void* stream) {
+    PYLC_REQUIRE(y_true && y_pred && cm && n > 0 && C >= 2 && C <= SCORE_MAXC, "%s: bad arguments", who);
+    PYLC_REQUIRE((true_bytes == 1 || true_bytes == 8) && (pred_bytes == 1 || pred_bytes == 8), "%s: masks must be uint8 or int64", who);
+    confusion_launch<IGN>(y_true, true_bytes, y_pred, pred_bytes, n, C, force_coverage, cm, ignore, skipped, as_stream(stream));
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_confusion_matrix(const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C,
+                                     int force_coverage, unsigned long long* cm /* [C*C], zeroed by the caller */, void* stream) {
+    return confusion_impl<false>("confusion_matrix", y_true, true_bytes, y_pred, pred_bytes, n, C, force_coverage, cm, 0, nullptr, stream);
+}
+
+extern "C" int pylc_confusion_matrix_ex(const void* y_true, int true_bytes, const void* y_pred, int pred_bytes, long long n, int C,
+                                        int force_coverage, unsigned long long* cm /* [C*C], zeroed by the caller */, int ignore_index,
+                                        unsigned long long* n_skipped /* [2]: bad, ignored; ADDED into; may be NULL */, void* stream) {
+    return confusion_impl<true>("confusion_matrix_ex", y_true, true_bytes, y_pred, pred_bytes, n, C, force_coverage, cm, (long long)ignore_index,
+                                n_skipped, stream);
 }

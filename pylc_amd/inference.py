@@ -12,6 +12,7 @@ steps after the stitch are pylc_amd.photo (segment_photo); the functions here ta
 A U-Net of valid convolutions returns the centred (tile - 2*pad)^2 square of its window, which reconstruct() cannot stitch; its
 images take the overlap-tile path instead (predict_overlap_tile, csrc/overlap_tile.hip): mirror-padded windows around output tiles
 that cover the image exactly, at any image size, blended by the mean of the tiles' softmax probabilities."""
+import contextlib
 import ctypes as C
 
 import torch
@@ -57,9 +58,64 @@ def tile_grid(h, w, tile, stride):
     return (h - tile) // stride + 1, (w - tile) // stride + 1
 
 
+# ---- the one driver: an image prepared for a model, the network's eval mode, this rank's tile batches through the network ------------
+class _TileRun:
+    """What every full-image path prepares from (model, image) before its first tile: the image on the model's device (uint8 stays
+    uint8 -- a photograph: a quarter of the bytes to upload, normalised straight from them -- everything else goes to float32), the
+    channel check, the normalisation statistics as the cutter takes them, the class count and its NHWC pitch, and this process's place
+    in `group` (world 1, rank 0 without one)."""
+
+    def __init__(self, model, image, group):
+        self.model, self.dev = model, model.device
+        u8 = image.dtype == torch.uint8
+        self.img = image.to(self.dev, dtype=torch.uint8 if u8 else torch.float32).contiguous()
+        if self.img.shape[0] != model.meta.ch:
+            raise ValueError('model expects %d-channel images' % model.meta.ch)
+        self.h, self.w = self.img.shape[1:]
+        mean, std, denom = model._stats(model.meta.normalize_default)
+        if denom != 255.0:              # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
+            std = [v * denom / 255.0 for v in std]
+        self.mean = (C.c_float * 3)(*[float(v) for v in mean])
+        self.std = (C.c_float * 3)(*[float(v) for v in std])
+        self.ncls = model.meta.n_classes
+        self.cp = (self.ncls + 3) & ~3
+        self.world = dist.get_world_size(group) if group is not None else 1
+        self.rank = dist.get_rank(group) if group is not None else 0
+
+    def mine(self, n_tiles, batch):
+        """this rank's (first tile, count) batches of an image of n_tiles"""
+        return shard_batches(n_tiles, batch, self.rank, self.world)
+
+    def batches(self, mine, tile, out, stride, member=0, img=None):
+        """For each (first tile, count) of `mine`: the windows cut from the image (or from `img`, another size of it) by the any-size
+        cutter -- the fitted grid is its case out == tile on a fitted image -- mirrored along x for member 1, through the network.
+        Yields (first tile, count, the network's output).  Call under _eval_mode."""
+        img = self.img if img is None else img
+        cimg, h, w = img.shape
+        for k, b in mine:
+            x4 = ops.empty_nhwc(b, 4, tile, tile, self.dev)
+            check(lib.pylc_image_pack_tiles_reflect_ex(ptr(img), int(img.dtype == torch.uint8), cimg, h, w, tile, out, stride, k, b, self.mean,
+                                                       self.std, ptr(x4), stream(), member))
+            yield k, b, self.model.net(x4)
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """The network in eval mode with current weight ranges and prepared filter planes (optim.refresh_if_changed has the reason), no
+    autograd; its mode comes back whatever happens inside."""
+    was_training = model.net.training
+    model.net.eval()
+    try:
+        model._refresh_for_inference()
+        with torch.no_grad():
+            yield
+    finally:
+        model.net.train(was_training)
+
+
 def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blend='reference', flip=False, return_probs=False,
                   return_confidence=False, scales=None, scale_weights=None):
-    """image: [C,H,W] raw 0..255 float tensor (host or device), fitted.  Returns the uint8 class mask [H,W] (device).
+    """image: [C,H,W] raw 0..255, uint8 or float (host or device), fitted.  Returns the uint8 class mask [H,W] (device).
 
     group=None (default): LOCAL -- this process runs every tile and returns the mask, also inside a data-parallel job (a rank-0-only
     validation preview must not hang in a collective).  With an explicit process group the call is a COLLECTIVE that every rank of the
@@ -89,44 +145,25 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blen
                          % ', '.join(asked))
     L.init()
     stride = tile // 2 if stride is None else stride          # test.py:63
-    dev = model.device
-    img = image.to(dev, dtype=torch.float32).contiguous()
-    cimg, h, w = img.shape
-    if cimg != model.meta.ch:
-        raise ValueError('model expects %d-channel images' % model.meta.ch)
-    rows, cols = tile_grid(h, w, tile, stride)
-    n = rows * cols
-    mean, std, denom = model._stats(model.meta.normalize_default)
-    if denom != 255.0:                  # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
-        std = [v * denom / 255.0 for v in std]
-    world = dist.get_world_size(group) if group is not None else 1
-    rank = dist.get_rank(group) if group is not None else 0
-    mine = shard_batches(n, batch, rank, world)
-    m = (C.c_float * 3)(*[float(v) for v in mean])
-    s = (C.c_float * 3)(*[float(v) for v in std])
-    ncls = model.meta.n_classes
-    cp = (ncls + 3) & ~3
-    logits = torch.empty((sum(c for _, c in mine), tile, tile, cp), device=dev)
-    was_training = model.net.training
-    model.net.eval()
-    with torch.no_grad():
+    run = _TileRun(model, image, group)
+    rows, cols = tile_grid(run.h, run.w, tile, stride)
+    n, cp = rows * cols, run.cp
+    mine = run.mine(n, batch)
+    logits = torch.empty((sum(c for _, c in mine), tile, tile, cp), device=run.dev)
+    with _eval_mode(model):
         pos = 0
-        for k, b in mine:
-            x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
-            check(lib.pylc_image_pack_tiles(ptr(img), cimg, h, w, tile, stride, k, b, m, s, ptr(x4), stream()))
-            y = model.net(x4)                                  # [b, ncls, tile', tile'] NHWC memory, pitch cp
+        for _, b, y in run.batches(mine, tile, tile, stride):  # [b, ncls, tile', tile'] NHWC memory, pitch cp
             if y.shape[2] != tile or y.shape[3] != tile:
                 raise ValueError('sliding-window stitching needs a same-size network (DeepLab); got %s' % (tuple(y.shape),))
-            logits[pos:pos + b].copy_(torch.as_strided(y, (b, tile, tile, cp), (tile * tile * ops.pitch_of(y), tile * ops.pitch_of(y), ops.pitch_of(y), 1),
-                                                       y.storage_offset()))
+            p = ops.pitch_of(y)
+            logits[pos:pos + b].copy_(torch.as_strided(y, (b, tile, tile, cp), (tile * tile * p, tile * p, p, 1), y.storage_offset()))
             pos += b
-    model.net.train(was_training)
-    if world > 1:
+    if run.world > 1:
         logits = gather_tiles(logits, n, batch, group)
         if logits is None:
             return None
-    mask = torch.empty((rows * stride + tile - stride, cols * stride + tile - stride), device=dev, dtype=torch.uint8)
-    check(lib.pylc_stitch_argmax(ptr(logits), cp, rows, cols, tile, stride, ncls, ptr(mask), stream()))
+    mask = torch.empty((run.h, run.w), device=run.dev, dtype=torch.uint8)
+    check(lib.pylc_stitch_argmax(ptr(logits), cp, rows, cols, tile, stride, run.ncls, ptr(mask), stream()))
     return mask
 
 
@@ -194,44 +231,21 @@ def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=Non
     if flip or return_confidence or scales is not None or scale_weights is not None:
         return predict_blend_mean(model, image, tile, out, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights)
     stride = out if stride is None else int(stride)
-    dev = model.device
-    u8 = image.dtype == torch.uint8            # a photograph: a quarter of the bytes to upload, normalised straight from them
-    img = image.to(dev, dtype=torch.uint8 if u8 else torch.float32).contiguous()
-    cimg, h, w = img.shape
-    if cimg != model.meta.ch:
-        raise ValueError('model expects %d-channel images' % model.meta.ch)
-    row_o, col_o = overlap_tile_grid(h, w, out, stride, pad)
-    n = len(row_o) * len(col_o)
-    mean, std, denom = model._stats(model.meta.normalize_default)
-    if denom != 255.0:                  # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
-        std = [v * denom / 255.0 for v in std]
-    world = dist.get_world_size(group) if group is not None else 1
-    rank = dist.get_rank(group) if group is not None else 0
-    mine = shard_batches(n, batch, rank, world)
-    m = (C.c_float * 3)(*[float(v) for v in mean])
-    s = (C.c_float * 3)(*[float(v) for v in std])
-    ncls = model.meta.n_classes
-    cp = (ncls + 3) & ~3
-    logits = torch.empty((sum(c for _, c in mine), out, out, cp), device=dev)
-    was_training = model.net.training
-    model.net.eval()
-    try:
-        model._refresh_for_inference()
-        with torch.no_grad():
-            pos = 0
-            for k, b in mine:
-                x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
-                check(lib.pylc_image_pack_tiles_reflect(ptr(img), int(u8), cimg, h, w, tile, out, stride, k, b, m, s, ptr(x4), stream()))
-                y = ops.as_nhwc(model.net(x4))                     # [b, ncls, out, out], NHWC memory
-                logits[pos:pos + b, :, :, :ncls].copy_(y.permute(0, 2, 3, 1))
-                pos += b
-    finally:
-        model.net.train(was_training)
-    if world > 1:
+    run = _TileRun(model, image, group)
+    row_o, col_o = overlap_tile_grid(run.h, run.w, out, stride, pad)
+    n, cp, ncls = len(row_o) * len(col_o), run.cp, run.ncls
+    mine = run.mine(n, batch)
+    logits = torch.empty((sum(c for _, c in mine), out, out, cp), device=run.dev)
+    with _eval_mode(model):
+        pos = 0
+        for _, b, y in run.batches(mine, tile, out, stride):
+            logits[pos:pos + b, :, :, :ncls].copy_(ops.as_nhwc(y).permute(0, 2, 3, 1))     # [b, ncls, out, out], NHWC memory
+            pos += b
+    if run.world > 1:
         logits = gather_tiles(logits, n, batch, group)
         if logits is None:
             return None
-    return _stitch_overlap(logits, cp, n, h, w, out, stride, ncls, return_probs)
+    return _stitch_overlap(logits, cp, n, run.h, run.w, out, stride, ncls, return_probs)
 
 
 SCALE_RANGE = (0.5, 2.0)    # where the plain bilinear resize still reads every source pixel (no area prefilter)
@@ -284,32 +298,22 @@ def ensemble_plan(scales, scale_weights, h, w, out):
     return plan
 
 
-def _blend_sweep(model, img, tile, out, stride, batch, group, members, norm):
-    """predict_blend_mean's sweep over one device image [C,H,W] (uint8 or float32): this rank's share of the tile batches, member-major,
-    into a zeroed accumulation image [H,W,cp], which it returns.  The network is in eval mode already."""
-    dev = model.device
-    u8 = img.dtype == torch.uint8
-    cimg, h, w = img.shape
+def _blend_sweep(run, img, tile, out, stride, batch, members):
+    """predict_blend_mean's sweep over one device image [C,H,W] (uint8 or float32; run.img or another size of it): this rank's share of
+    the tile batches, member-major, into a zeroed accumulation image [H,W,cp], which it returns.  The network is in eval mode already."""
+    h, w = img.shape[1:]
     row_o, col_o = overlap_tile_grid(h, w, out, stride, (tile - out) // 2)
-    n = len(row_o) * len(col_o)
-    world = dist.get_world_size(group) if group is not None else 1
-    rank = dist.get_rank(group) if group is not None else 0
-    mine = shard_batches(n, batch, rank, world)
-    m, s = norm
-    ncls = model.meta.n_classes
-    cp = (ncls + 3) & ~3
-    acc = torch.zeros((h, w, cp), device=dev)
+    mine = run.mine(len(row_o) * len(col_o), batch)
+    ncls, cp = run.ncls, run.cp
+    acc = torch.zeros((h, w, cp), device=run.dev)
     for member in range(members):                   # member-major: the sums of member 0 are complete before member 1 adds to them
-        for k, b in mine:
-            x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
-            check(lib.pylc_image_pack_tiles_reflect_ex(ptr(img), int(u8), cimg, h, w, tile, out, stride, k, b, m, s, ptr(x4), stream(),
-                                                       member))
-            y = ops.as_nhwc(model.net(x4))                     # [b, ncls, out, out], NHWC memory
+        for k, b, y in run.batches(mine, tile, out, stride, member, img):
+            y = ops.as_nhwc(y)                                  # [b, ncls, out, out], NHWC memory
             if tuple(y.shape[1:]) != (ncls, out, out):
                 raise ValueError('the network returned %s for %d px windows, not %d classes of %d px' % (tuple(y.shape), tile, ncls, out))
             p = ops.pitch_of(y)
             if p % 4 or y.data_ptr() % 16:                      # a pitch the 16-byte loads cannot take: one relayout to pitch cp
-                y2 = ops.zeros_nhwc(b, ncls, out, out, dev, pitch=cp)
+                y2 = ops.zeros_nhwc(b, ncls, out, out, run.dev, pitch=cp)
                 y2.copy_(y)
                 y, p = y2, cp
             check(lib.pylc_blend_accumulate(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream()))
@@ -350,45 +354,26 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
         raise ValueError('scale_weights needs scales')
     plan = None if scales is None else ensemble_plan(scales, scale_weights, image.shape[1], image.shape[2], out)    # before any launch
     L.init()
-    dev = model.device
-    u8 = image.dtype == torch.uint8
-    img = image.to(dev, dtype=torch.uint8 if u8 else torch.float32).contiguous()
-    cimg, h, w = img.shape
-    if cimg != model.meta.ch:
-        raise ValueError('model expects %d-channel images' % model.meta.ch)
+    run = _TileRun(model, image, group)
+    img, h, w, ncls, cp = run.img, run.h, run.w, run.ncls, run.cp
     overlap_tile_grid(h, w, out, stride, (tile - out) // 2)            # the geometry's errors before the network's mode is touched
-    mean, std, denom = model._stats(model.meta.normalize_default)
-    if denom != 255.0:                  # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
-        std = [v * denom / 255.0 for v in std]
-    world = dist.get_world_size(group) if group is not None else 1
-    rank = dist.get_rank(group) if group is not None else 0
-    norm = ((C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std]))
-    ncls = model.meta.n_classes
-    cp = (ncls + 3) & ~3
     members = 2 if flip else 1
     acc = ens = None
-    was_training = model.net.training
-    model.net.eval()
-    try:
-        model._refresh_for_inference()
-        with torch.no_grad():
-            if plan is None:
-                acc = _blend_sweep(model, img, tile, out, stride, batch, group, members, norm)
-            else:
-                ens = torch.empty((h, w, cp), device=dev)             # the first scale's launch writes every channel below ncls
-                for k, (_, hs, ws, wgt) in enumerate(plan):
-                    acc_s = _blend_sweep(model, img if (hs, ws) == (h, w) else resize_image(img, hs, ws), tile, out, stride, batch, group,
-                                         members, norm)
-                    check(lib.pylc_blend_resample_accumulate(ptr(acc_s), cp, hs, ws, out, stride, members, wgt, ncls, ptr(ens), cp, h, w,
-                                                             int(k > 0), stream()))
-                    del acc_s
-    finally:
-        model.net.train(was_training)
-    if world > 1:
+    with _eval_mode(model):
+        if plan is None:
+            acc = _blend_sweep(run, img, tile, out, stride, batch, members)
+        else:
+            ens = torch.empty((h, w, cp), device=run.dev)             # the first scale's launch writes every channel below ncls
+            for k, (_, hs, ws, wgt) in enumerate(plan):
+                acc_s = _blend_sweep(run, img if (hs, ws) == (h, w) else resize_image(img, hs, ws), tile, out, stride, batch, members)
+                check(lib.pylc_blend_resample_accumulate(ptr(acc_s), cp, hs, ws, out, stride, members, wgt, ncls, ptr(ens), cp, h, w,
+                                                         int(k > 0), stream()))
+                del acc_s
+    if run.world > 1:
         if plan is not None:
             ens[..., ncls:] = 0                                   # the padding channels were never written: keep the collective off garbage
         dist.all_reduce(acc if plan is None else ens, group=group)
-        if rank != 0:
+        if run.rank != 0:
             return None
     if plan is None:
         return _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence)

@@ -19,15 +19,13 @@ A U-Net takes only the scale step and then predict_overlap_tile, which accepts a
 nothing to match there -- it cannot run a U-Net on a photograph at all (reconstruct() assumes same-size tiles).  A DeepLab asked for
 blend='mean' takes the same route through the streaming mean-probability blend (inference.predict_blend_mean), which
 is what gives it probabilities, a confidence map and a flip ensemble."""
-import ctypes as C
 import math
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
-from . import boundary, metrics, ops, regions, lib as L
-from .inference import gather_tiles, predict_blend_mean, predict_overlap_tile, shard_batches, tile_grid
+from . import boundary, metrics, regions, lib as L
+from .inference import predict_blend_mean, predict_image, predict_overlap_tile
 from .lib import lib, check, ptr, stream
 
 MAX_CLASSES = 16            # PYLC_MAX_CLASSES (include/pylc_hip.h)
@@ -163,45 +161,6 @@ def _encode(rgb, pal):
     return out
 
 
-# ---- the sliding window on a fitted uint8 image (predict_image's path, pylc_image_pack_tiles_ex) ------------------------------------
-def _predict_fitted(model, img, tile, stride, batch, group):
-    """predict_image (inference.py) on a device uint8 [C,H,W] fitted image: tiles cut by pylc_image_pack_tiles_ex, which gives the same
-    bytes as the float cutter, so the mask is bit-identical to predict_image on img.float()."""
-    dev = model.device
-    cimg, h, w = img.shape
-    rows, cols = tile_grid(h, w, tile, stride)
-    n = rows * cols
-    mean, std, denom = model._stats(model.meta.normalize_default)
-    if denom != 255.0:                  # the tile cutter divides by 255: fold the grayscale-defaults branch's missing division into std
-        std = [v * denom / 255.0 for v in std]
-    world = dist.get_world_size(group) if group is not None else 1
-    rank = dist.get_rank(group) if group is not None else 0
-    mine = shard_batches(n, batch, rank, world)
-    m = (C.c_float * 3)(*[float(v) for v in mean])
-    s = (C.c_float * 3)(*[float(v) for v in std])
-    ncls = model.meta.n_classes
-    cp = (ncls + 3) & ~3
-    logits = torch.empty((sum(c for _, c in mine), tile, tile, cp), device=dev)
-    with torch.no_grad():
-        pos = 0
-        for k, b in mine:
-            x4 = ops.empty_nhwc(b, 4, tile, tile, dev)
-            check(lib.pylc_image_pack_tiles_ex(ptr(img), 1, cimg, h, w, tile, stride, k, b, m, s, ptr(x4), stream()))
-            y = model.net(x4)
-            if y.shape[2] != tile or y.shape[3] != tile:
-                raise ValueError('sliding-window stitching needs a same-size network (DeepLab); got %s' % (tuple(y.shape),))
-            p = ops.pitch_of(y)
-            logits[pos:pos + b].copy_(torch.as_strided(y, (b, tile, tile, cp), (tile * tile * p, tile * p, p, 1), y.storage_offset()))
-            pos += b
-    if world > 1:
-        logits = gather_tiles(logits, n, batch, group)
-        if logits is None:
-            return None
-    mask = torch.empty((h, w), device=dev, dtype=torch.uint8)
-    check(lib.pylc_stitch_argmax(ptr(logits), cp, rows, cols, tile, stride, ncls, ptr(mask), stream()))
-    return mask
-
-
 class PhotoResult:
     """segment_photo's output.  mask: device uint8 [h_scaled, w_scaled] class indices; rgb: device uint8 [h_scaled, w_scaled, 3] when a
     palette was given (else None); geometry: fit_geometry's dict; probs: the mean softmax probabilities [n_classes, h_scaled, w_scaled]
@@ -271,39 +230,34 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     L.init()
     dev = model.device
     pal = _palette_tensor(palette, model.meta.n_classes, dev) if palette is not None else None
-    was_training = model.net.training
-    model.net.eval()
-    try:
-        if unet or blend == 'mean':
-            h_s, w_s = scaled_size(shape[0], shape[1], tile, scale)
-            if h_s > shape[0] or w_s > shape[1] or h_s == 0 or w_s == 0:
-                raise ValueError('photograph %dx%d (HxW) at scale %s gives %dx%d: INTER_AREA downscales only here' % (shape[0], shape[1], scale,
-                                                                                                                       h_s, w_s))
-            geom = {'w_full': shape[1], 'h_full': shape[0], 'w_scaled': w_s, 'h_scaled': h_s, 'w_fitted': w_s, 'h_fitted': h_s,
-                    'offset': 0}                      # Extractor.extract(fit=False): (img, w_scaled, h_scaled, 0)
-            img = resize_area(_upload_photo(image, dev), h_s, w_s)      # at its own size: a relayout to [C,H,W]
-            if unet:
-                got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights)
-            else:
-                got = predict_blend_mean(model, img, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales,
-                                         scale_weights)
-            if got is None:
-                return None
-            got = list(got) if isinstance(got, tuple) else [got]
-            mask = got.pop(0)
-            probs = got.pop(0) if return_probs else None
-            conf = got.pop(0) if return_confidence else None
-            rgb = None
-            if pal is not None:
-                rgb = _colourize(mask, pal, h_s, w_s)
-                mask = _encode(rgb, pal)
-            res = PhotoResult(mask, rgb, geom, probs, tile, scale, conf)
-            return _sieve_result(res, pal, int(min_region), region_connectivity, region_fill, ignore_index) if sieving else res
-        stride = tile // 2 if stride is None else stride          # test.py:63
-        img, geom = fit_image(image, tile, stride, scale, dev)
-        fitted = _predict_fitted(model, img, tile, stride, batch, group)
-    finally:
-        model.net.train(was_training)
+    if unet or blend == 'mean':
+        h_s, w_s = scaled_size(shape[0], shape[1], tile, scale)
+        if h_s > shape[0] or w_s > shape[1] or h_s == 0 or w_s == 0:
+            raise ValueError('photograph %dx%d (HxW) at scale %s gives %dx%d: INTER_AREA downscales only here' % (shape[0], shape[1], scale,
+                                                                                                                   h_s, w_s))
+        geom = {'w_full': shape[1], 'h_full': shape[0], 'w_scaled': w_s, 'h_scaled': h_s, 'w_fitted': w_s, 'h_fitted': h_s,
+                'offset': 0}                      # Extractor.extract(fit=False): (img, w_scaled, h_scaled, 0)
+        img = resize_area(_upload_photo(image, dev), h_s, w_s)      # at its own size: a relayout to [C,H,W]
+        if unet:
+            got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights)
+        else:
+            got = predict_blend_mean(model, img, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales,
+                                     scale_weights)
+        if got is None:
+            return None
+        got = list(got) if isinstance(got, tuple) else [got]
+        mask = got.pop(0)
+        probs = got.pop(0) if return_probs else None
+        conf = got.pop(0) if return_confidence else None
+        rgb = None
+        if pal is not None:
+            rgb = _colourize(mask, pal, h_s, w_s)
+            mask = _encode(rgb, pal)
+        res = PhotoResult(mask, rgb, geom, probs, tile, scale, conf)
+        return _sieve_result(res, pal, int(min_region), region_connectivity, region_fill, ignore_index) if sieving else res
+    stride = tile // 2 if stride is None else stride          # test.py:63
+    img, geom = fit_image(image, tile, stride, scale, dev)
+    fitted = predict_image(model, img, tile, stride, batch, group)           # the uint8 fitted image is cut as uint8
     if fitted is None:
         return None
     h_s, w_s = geom['h_scaled'], geom['w_scaled']

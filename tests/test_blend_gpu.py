@@ -378,7 +378,7 @@ def test_segment_photo_deeplab_mean_blend(dev, deeplab):
 
 
 def test_segment_photo_default_is_the_reference_round_trip(dev, deeplab):
-    """The default call is what it was: _predict_fitted on the fitted image, colourize + nearest resize back, encode."""
+    """The default call is what it was: predict_image on the uint8 fitted image, colourize + nearest resize back, encode."""
     from pylc_amd import inference, photo
     model = deeplab['model']
     from tests.test_photo_gpu import photo_np
@@ -386,7 +386,7 @@ def test_segment_photo_default_is_the_reference_round_trip(dev, deeplab):
     res = photo.segment_photo(model, image, tile=64)
     fitted, g = photo.fit_image(image, 64, 32, None, dev)
     assert (g['h_fitted'], g['w_fitted']) == (128, 192)
-    fm = photo._predict_fitted(model, fitted, 64, 32, 8, None)
+    fm = inference.predict_image(model, fitted, 64, 32)
     ident = np.repeat(np.arange(9, dtype=np.uint8)[:, None], 3, 1)
     want = photo.encode_mask(inference.colourize(fm, ident, 180, 230), ident)
     assert torch.equal(res.mask, want) and res.probs is None and res.confidence is None and res.rgb is None
