@@ -276,9 +276,16 @@ def test_dwconv(dev, c, stride, dil, hw):
         assert rel_err(sums[:c], yd.sum((0, 2, 3))) < 1e-5 and rel_err(sums[c:], (yd * yd).sum((0, 2, 3))) < 1e-5
 
 
-@pytest.mark.parametrize('c,b,hw,relu,res', [(64, 4, 16, True, False), (256, 2, 9, True, True), (48, 3, 11, True, False),
-                                             (728, 2, 6, False, False), (2048, 2, 4, True, True), (256, 5, 1, True, False)])
-def test_bn_train(dev, c, b, hw, relu, res):
+# (c, b, hw, relu, res, extra pitch of y); 1536 channels: a partial second column pass (Xception exit flow); 20: an odd vector count; the
+# last one reads y at pitch C + 4 out of a wider NHWC buffer.  The ids of the first six are the ones they always had.
+BN_TRAIN = [(64, 4, 16, True, False, 0), (256, 2, 9, True, True, 0), (48, 3, 11, True, False, 0), (728, 2, 6, False, False, 0),
+            (2048, 2, 4, True, True, 0), (256, 5, 1, True, False, 0), (1536, 2, 5, True, True, 0), (20, 3, 5, True, False, 0),
+            (48, 3, 11, True, True, 4)]
+
+
+@pytest.mark.parametrize('c,b,hw,relu,res,extra', [pytest.param(*t, id='-'.join(map(str, t[:5])) + ('-pitch+%d' % t[5] if t[5] else ''))
+                                                   for t in BN_TRAIN])
+def test_bn_train(dev, c, b, hw, relu, res, extra):
     from pylc_amd import ops
     y = rnd(11, b, c, hw, hw, scale=2.0) + 0.5
     g, be = 1 + 0.1 * rnd(12, c), 0.1 * rnd(13, c)
@@ -294,7 +301,13 @@ def test_bn_train(dev, c, b, hw, relu, res):
         o = F.relu(o)
     do = rnd(17, *o.shape)
     o.backward(do.double())
-    yd = to_dev_nhwc(y, dev).requires_grad_(True)
+    if extra:
+        wide = torch.full((b, c + extra, hw, hw), float('nan'), device=dev).contiguous(memory_format=torch.channels_last)
+        wide[:, :c] = y.to(dev)
+        yd = wide[:, :c].detach().requires_grad_(True)
+        assert yd.stride(3) == c + extra and yd.stride(1) == 1
+    else:
+        yd = to_dev_nhwc(y, dev).requires_grad_(True)
     gd, bed = g.to(dev).requires_grad_(True), be.to(dev).requires_grad_(True)
     rmd, rvd = rm.to(dev), rv.to(dev)
     rd = to_dev_nhwc(r, dev).requires_grad_(True) if res else None
