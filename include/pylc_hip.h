@@ -839,6 +839,15 @@ int pylc_boundary_counts(const unsigned char* truth, const unsigned char* pred, 
  * pylc_boundary_distance(pred, ignore_from = truth), N = B*H*W pixels.  One launch. */
 int pylc_boundary_counts_maps(const unsigned char* truth, const unsigned char* pred, const int* d2_truth, const int* d2_pred, long long N,
                               int n_classes, int radius, int ignore_index, unsigned long long* counts, void* stream);
+/* Border weights: out[p] = d2(p) < 0 ? 0 : table[d2(p)], float32 [B][H][W], with d2 as pylc_boundary_distance
+ * gives it and table a device float32 [radius*radius + 2] (the last cell is the saturated distance).  The column pass and the row
+ * pass of the distance with a storing epilogue: two launches, no int32 map.  Workspace: pylc_boundary_workspace_bytes.  table, out
+ * and workspace 4-B aligned.  Argument errors as for pylc_boundary_distance: PYLC_ERR_ARG, nothing is launched. */
+int pylc_boundary_weights(const unsigned char* mask, int B, int H, int W, int radius, int ignore_index, const float* table, float* out,
+                          void* workspace, void* stream);
+/* The same lookup over a d2 map that pylc_boundary_distance wrote with this radius, N = B*H*W pixels (1 <= N < 2^31).  One launch.
+ * A value above radius*radius + 1 reads the last cell. */
+int pylc_weights_from_d2(const int* d2, long long N, int radius, const float* table, float* out, void* stream);
 
 /* The general form: ((x - mean[c]) / std[c]) / denom on float (is_u8 = 0) or uint8 (is_u8 = 1) tiles.  denom = 255 is
  * pylc_image_pack[_u8]; denom = 1 is the reference's grayscale `default=True` branch, which omits the division by 255
@@ -890,6 +899,20 @@ int pylc_multiloss_finalize_ex(const float* stats, int C, float w_ce, float w_di
 int pylc_multiloss_bwd_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
                           const float* class_weights, const float* stats, float w_ce, float w_dice, float w_focal,
                           const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream);
+/* With a weight per pixel: pixel_weights is float32 [N] (4-B aligned), u_n.  A pixel takes part when its target
+ * is valid as above and 0 < u_n <= FLT_MAX; u_n == 0 is skipped like an ignored pixel, a negative, NaN or infinite u_n is skipped and
+ * counted in n_bad (the target is judged first).  CE = sum u w_t (-log p_t) / sum u w_t; Dice with I_c = sum u o_c p_c, sum u p_c and
+ * count_c = sum u o_c; Focal = sum u f_n / sum u; dlogits row n = u_n times the row of the closed form evaluated with these sums.  The
+ * stats keep their layout (stats[1] = sum u w_t, the class counts sum to sum u), so pylc_multiloss_finalize_ex finalises them.  The
+ * weighted class counts are fp32 sums of non-integers: rounded, no longer exact.  pixel_weights == NULL runs the kernels of _ex; a
+ * map of 1.0f gives their bits.  ignore_index INT32_MIN: no target is ignored.  Argument errors as for _ex, and a pixel_weights
+ * pointer that is not 4-B aligned: PYLC_ERR_ARG, nothing is launched. */
+int pylc_multiloss_stats_w(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                           const float* class_weights, const float* pixel_weights, float* stats, float* workspace,
+                           unsigned long long* n_bad, void* stream);
+int pylc_multiloss_bwd_w(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                         const float* class_weights, const float* pixel_weights, const float* stats, float w_ce, float w_dice,
+                         float w_focal, const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimiser: torch.nn.utils.clip_grad_norm_(params, 0.5) models/model.py:326 + torch.optim.AdamW

@@ -8,7 +8,10 @@ in its mask's band when d2 <= R*R.  Everything is integer work: a numpy statemen
 
 Counts of a (truth, prediction) pair, int64 [C*C + 3C + 1]: cm_band [C,C] over the truth's band (the trimap confusion matrix), then
 inter / gband / pband [C] each, then one cell for values outside 0..C-1 that are not the ignore label.  Where the truth is ignored the
-prediction counts as ignored before its distances are taken; only pixels with a labelled truth are counted."""
+prediction counts as ignored before its distances are taken; only pixels with a labelled truth are counted.
+
+Border weights: border_profile is a table over d2, border_weights the float32 map table[d2] of a mask (0 at ignored
+pixels) in the distance's two launches -- the per-pixel weights of ops.multiloss(pixel_weights=) and Meta.border_weight."""
 import math
 
 import numpy as np
@@ -89,6 +92,63 @@ def boundary_band(mask, radius, ignore_index=None):
     """Device uint8 mask -> bool of the same shape: the labelled pixels within `radius` of a pixel of another class."""
     d2 = boundary_distance(mask, radius, ignore_index)
     return (d2 >= 0) & (d2 <= int(radius) * int(radius))
+
+
+def border_profile(radius, w0=10.0, sigma=5.0):
+    """The weight table of a border-weighted loss, float32 numpy [R*R + 2], indexed by d2: 1 + w0 exp(-d2 / (2 sigma^2))
+    for d2 <= R*R (the U-Net paper's profile over one distance), computed in float64 and rounded once; the saturated last cell (no other
+    class within R) is 1.  w0 >= 0, sigma > 0."""
+    radius = _check_radius(radius)
+    w0, sigma = float(w0), float(sigma)
+    if not (math.isfinite(w0) and w0 >= 0.0):
+        raise ValueError('w0=%r must be a finite number >= 0' % (w0,))
+    if not (math.isfinite(sigma) and sigma > 0.0):
+        raise ValueError('sigma=%r must be a finite number > 0' % (sigma,))
+    d2 = np.arange(radius * radius + 2, dtype=np.float64)
+    table = 1.0 + w0 * np.exp(-d2 / (2.0 * sigma * sigma))
+    table[-1] = 1.0
+    return table.astype(np.float32)
+
+
+def _check_table(table, radius, device):
+    """-> contiguous float32 device tensor [R*R + 2] of a numpy array or tensor"""
+    cells = radius * radius + 2
+    if isinstance(table, np.ndarray):
+        table = torch.from_numpy(np.ascontiguousarray(table))
+    if not torch.is_tensor(table) or table.dtype != torch.float32 or table.dim() != 1 or table.numel() != cells:
+        raise ValueError('a weight table of radius %d must be float32 [%d] (border_profile)' % (radius, cells))
+    return table.to(device).contiguous()
+
+
+def border_weights(mask, radius, table=None, w0=10.0, sigma=5.0, ignore_index=None):
+    """Device uint8 [H,W] or [B,H,W] -> float32 of the same shape: table[d2] of boundary_distance(mask, radius, ignore_index), 0 at pixels
+    equal to ignore_index -- the per-pixel weights of ops.multiloss(pixel_weights=).  table: float32 [R*R + 2] (numpy or tensor; a device
+    tensor is used as it is), by default border_profile(radius, w0, sigma).  Two launches, the int32 distance map is never written."""
+    radius, ign = _check_radius(radius), _check_ignore(ignore_index)
+    b, h, w = _check_mask(mask)
+    if table is None:
+        table = border_profile(radius, w0, sigma)
+    mask = _on_device(mask, 'a mask')
+    table = _check_table(table, radius, mask.device)
+    L.init()
+    out = torch.empty(mask.shape, device=mask.device, dtype=torch.float32)
+    ws = _workspace(b, h, w, mask.device)
+    check(lib.pylc_boundary_weights(ptr(mask), b, h, w, radius, ign, ptr(table), ptr(out), ptr(ws), stream()))
+    return out
+
+
+def weights_from_distance(d2, radius, table):
+    """border_weights for a distance map that exists: device int32 d2 = boundary_distance(mask, radius, ...) -> float32 table[d2], 0 where
+    d2 < 0.  One launch."""
+    radius = _check_radius(radius)
+    if not torch.is_tensor(d2) or d2.dtype != torch.int32 or d2.numel() == 0 or d2.numel() >= 2 ** 31:
+        raise ValueError('a distance map must be a non-empty int32 tensor (boundary_distance)')
+    d2 = _on_device(d2, 'd2')
+    table = _check_table(table, radius, d2.device)
+    L.init()
+    out = torch.empty(d2.shape, device=d2.device, dtype=torch.float32)
+    check(lib.pylc_weights_from_d2(ptr(d2), d2.numel(), radius, ptr(table), ptr(out), stream()))
+    return out
 
 
 def _check_pair(y_true, y_pred, n_classes, radius, ignore_index, counts):

@@ -29,6 +29,11 @@
 // runs' totals and the int64 counters one 64-bit atomic per non-zero cell and block.  Above BD_LDS_MAXC classes the C*C + 3C + 1 cells
 // are no sensible LDS array and the runs' totals go to the int64 counters directly.  pylc_boundary_counts_maps is the two-map form: the
 // same epilogue over two d2 maps written by pylc_boundary_distance (tools/boundary_bench.py times one against the other).
+//
+// Border weights (pylc_boundary_weights): the row pass with an epilogue that stores table[d2] as a float instead of
+// d2 -- the per-pixel weight of a border-weighted loss in the two launches of the distance, with no int32 map written and read back.  The
+// profile is the caller's table of R*R + 2 floats (no expf here: the result is a lookup, bit for bit what numpy's table[d2] gives).
+// pylc_weights_from_d2 is the one-launch form over a map that exists.
 #include "common.h"
 
 namespace pylc {
@@ -133,9 +138,23 @@ __device__ __forceinline__ int bd_row_d2(const unsigned short* at, int x, int W,
     return best;
 }
 
+// what the row pass does with a pixel's d2: write it, or write the weight it selects (pylc_boundary_weights: no int32 map in between)
+struct BdStoreD2 {
+    int* __restrict__ d2;
+    __device__ __forceinline__ void operator()(long long i, int v) const { d2[i] = v; }
+};
+
+// table: float [R*R + 2], indexed by d2 in 0..R*R + 1 (which bd_row_d2 never exceeds); an ignored pixel (-1) weighs 0
+struct BdStoreWeight {
+    const float* __restrict__ table;
+    float* __restrict__ out;
+    __device__ __forceinline__ void operator()(long long i, int v) const { out[i] = v < 0 ? 0.f : table[v]; }
+};
+
+template <typename Epilogue>
 __global__ __launch_bounds__(256) void bd_row_kernel(const unsigned char* __restrict__ mask, const unsigned char* __restrict__ from,
                                                      const unsigned char* __restrict__ g, int H, int W, int Wp, int tiles_x, int tiles_y, int R,
-                                                     int ign, int* __restrict__ d2) {
+                                                     int ign, Epilogue store) {
     extern __shared__ unsigned short bd_rows[];        // BD_RW_TH rows of BD_RW_TW + 2 R words
     unsigned int t = blockIdx.x;
     const int tx0 = (int)(t % (unsigned)tiles_x) * BD_RW_TW;
@@ -151,7 +170,16 @@ __global__ __launch_bounds__(256) void bd_row_kernel(const unsigned char* __rest
     for (int k = 0; k < BD_RW_TH / 2; ++k) {
         const int r = (threadIdx.x >> 7) + 2 * k, y = ty0 + r;
         if (y >= H) break;
-        d2[(img * H + y) * W + x] = bd_row_d2(bd_rows + r * stride + R + lx, x, W, R, ign);
+        store((img * H + y) * W + x, bd_row_d2(bd_rows + r * stride + R + lx, x, W, R, ign));
+    }
+}
+
+// the one-launch form over a d2 map that was written out; a value above R*R + 1 (no map of this radius holds one) reads the last cell
+__global__ __launch_bounds__(256) void bd_weights_from_d2_kernel(const int* __restrict__ d2, long long N, int cap, const float* __restrict__ table,
+                                                                 float* __restrict__ out) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const int v = d2[i];
+        out[i] = v < 0 ? 0.f : table[v < cap ? v : cap];
     }
 }
 
@@ -354,8 +382,39 @@ extern "C" int pylc_boundary_distance(const unsigned char* mask, int B, int H, i
     bd_launch_column(mask, ignore_from, B, H, W, radius, ignore_index, g, st);
     const int tiles_x = cdiv(W, BD_RW_TW), tiles_y = cdiv(H, BD_RW_TH);
     const size_t lds = (size_t)BD_RW_TH * (BD_RW_TW + 2 * radius) * sizeof(unsigned short);
-    hipLaunchKernelGGL(bd_row_kernel, dim3((unsigned)((long long)B * tiles_x * tiles_y)), dim3(256), lds, st, mask, ignore_from, g, H, W, bd_pitch(W),
-                       tiles_x, tiles_y, radius, ignore_index, d2_out);
+    hipLaunchKernelGGL(bd_row_kernel<BdStoreD2>, dim3((unsigned)((long long)B * tiles_x * tiles_y)), dim3(256), lds, st, mask, ignore_from, g, H, W,
+                       bd_pitch(W), tiles_x, tiles_y, radius, ignore_index, BdStoreD2{d2_out});
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_boundary_weights(const unsigned char* mask, int B, int H, int W, int radius, int ignore_index, const float* table, float* out,
+                                     void* workspace, void* stream) {
+    PYLC_REQUIRE(mask && table && out && workspace, "boundary_weights: mask, table, out or workspace is NULL");
+    if (int rc = bd_check_shape("boundary_weights", B, H, W, radius, ignore_index)) return rc;
+    PYLC_REQUIRE(((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 3) == 0,
+                 "boundary_weights: table, out or workspace is not 4-byte aligned");
+    hipStream_t st = as_stream(stream);
+    unsigned char* g = static_cast<unsigned char*>(workspace);
+    bd_launch_column(mask, nullptr, B, H, W, radius, ignore_index, g, st);
+    const int tiles_x = cdiv(W, BD_RW_TW), tiles_y = cdiv(H, BD_RW_TH);
+    const size_t lds = (size_t)BD_RW_TH * (BD_RW_TW + 2 * radius) * sizeof(unsigned short);
+    hipLaunchKernelGGL(bd_row_kernel<BdStoreWeight>, dim3((unsigned)((long long)B * tiles_x * tiles_y)), dim3(256), lds, st, mask,
+                       static_cast<const unsigned char*>(nullptr), g, H, W, bd_pitch(W), tiles_x, tiles_y, radius, ignore_index,
+                       BdStoreWeight{table, out});
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_weights_from_d2(const int* d2, long long N, int radius, const float* table, float* out, void* stream) {
+    PYLC_REQUIRE(d2 && table && out, "weights_from_d2: d2, table or out is NULL");
+    PYLC_REQUIRE(N >= 1 && N < (1ll << 31), "weights_from_d2: N=%lld outside 1 <= N < 2^31", N);
+    PYLC_REQUIRE(radius >= 1 && radius <= BD_MAX_R, "weights_from_d2: radius=%d outside 1..%d", radius, BD_MAX_R);
+    PYLC_REQUIRE(((reinterpret_cast<uintptr_t>(d2) | reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(out)) & 3) == 0,
+                 "weights_from_d2: d2, table or out is not 4-byte aligned");
+    const long long want = cdiv<long long>(N, 256);
+    const unsigned blocks = (unsigned)(want < 8 * kNumCU ? want : 8 * kNumCU);
+    hipLaunchKernelGGL(bd_weights_from_d2_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), d2, N, radius * radius + 1, table, out);
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
 }

@@ -15,6 +15,18 @@
 // globally: a thread's and a block's partial counts are sums of ones in fp32 (exact below 2^24 per block, i.e. for N < 2^34),
 // column_sum_kernel adds the <= 1024 block partials in fp64 (exact), and only the final store of a class total to the fp32 stats (and a
 // data-parallel all-reduce of it) rounds -- to nearest, relative error <= 2^-25 per class beyond 2^24 pixels in it.
+//
+// Pixel weights (pylc_multiloss_*_w): PW adds a float weight u_n per pixel, read next to the target and before the
+// logits row.  A pixel takes part when its target is valid as above AND 0 < u_n <= FLT_MAX; u_n == 0 is skipped like an ignored pixel, a
+// negative, NaN or infinite u_n is skipped and counted in n_bad (the target is judged first: an ignored target is never counted, whatever
+// its weight).  u is ONE extra factor: u * w in the CE sum and its denominator, u on every Dice and Focal addend, gs * u on the gradient
+// row, so stats[1] = sum u w, the class counts are sum u o_c and their sum is sum u -- what finalize_ex and the backward divide by already.
+// Multiplying by exactly 1.0f changes no bit (the library is built with -ffp-contract=off and no existing operation is re-associated), so
+// u == 1 gives the bits of the _ex path; PW = false is the code as it was.  The exactness argument above holds as written whenever every
+// weight is 1; with other weights the class counts are fp32 sums of non-integers and round like every other sum of the statistics
+// (a block partial's relative error grows with the pixels a thread adds, as for sum p_c).
+#include <cfloat>
+
 #include "common.h"
 
 namespace pylc {
@@ -41,10 +53,13 @@ __device__ __forceinline__ void softmax_px(const float* __restrict__ z, float (&
 
 // partial[block][3 + 3C]
 // n_bad (IGN only, may be NULL): the number of skipped pixels that are not `ignore` is ADDED into it
-template <int C, typename TT, bool IGN>
+// PW (needs IGN): pw[n] weighs pixel n, see above; without PW pw is not read
+template <int C, typename TT, bool IGN, bool PW>
 __global__ __launch_bounds__(256) void multiloss_stats_kernel(const float* __restrict__ logits, int pitch, const TT* __restrict__ target,
                                                               long long N, const float* __restrict__ cw, float* __restrict__ partial,
-                                                              long long ignore, unsigned long long* __restrict__ n_bad) {
+                                                              long long ignore, unsigned long long* __restrict__ n_bad,
+                                                              const float* __restrict__ pw) {
+    static_assert(IGN || !PW, "pixel weights ride on the ignore path");
     __shared__ float red[4];
     float acc[3 + 3 * C];
 #pragma unroll
@@ -52,9 +67,15 @@ __global__ __launch_bounds__(256) void multiloss_stats_kernel(const float* __res
     unsigned int bad = 0;
     for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long long)gridDim.x * blockDim.x) {
         const long long tl = (long long)target[n];
+        float u = 1.f;
+        if constexpr (PW) u = pw[n];
         if constexpr (IGN) {
             if (tl == ignore) continue;
             if ((unsigned long long)tl >= (unsigned long long)C) { ++bad; continue; }
+        }
+        if constexpr (PW) {
+            if (u == 0.f) continue;
+            if (!(u > 0.f && u <= FLT_MAX)) { ++bad; continue; }      // negative, NaN, infinite
         }
         float z[C], p[C], lse;
         const float* src = logits + n * pitch;
@@ -68,16 +89,30 @@ __global__ __launch_bounds__(256) void multiloss_stats_kernel(const float* __res
             const bool is = (c == t);
             zt = is ? z[c] : zt;
             pt = is ? p[c] : pt;
-            acc[3 + c] += is ? p[c] : 0.f;        // I_c
-            acc[3 + C + c] += p[c];               // sum p_c
-            acc[3 + 2 * C + c] += is ? 1.f : 0.f; // count_c
+            if constexpr (PW) {
+                const float up = u * p[c];
+                acc[3 + c] += is ? up : 0.f;
+                acc[3 + C + c] += up;
+                acc[3 + 2 * C + c] += is ? u : 0.f;
+            } else {
+                acc[3 + c] += is ? p[c] : 0.f;        // I_c
+                acc[3 + C + c] += p[c];               // sum p_c
+                acc[3 + 2 * C + c] += is ? 1.f : 0.f; // count_c
+            }
         }
         const float w = cw != nullptr ? cw[t] : 1.f;
-        acc[0] += w * (lse - zt);                 // -log p_t via log-sum-exp (exact for saturated pixels)
-        acc[1] += w;
         const float q = pt + kFlEps;
         const float omq = 1.f - q;
-        acc[2] += -kFlAlpha * omq * omq * logf(q);
+        if constexpr (PW) {
+            const float uw = u * w;
+            acc[0] += uw * (lse - zt);
+            acc[1] += uw;
+            acc[2] += u * (-kFlAlpha * omq * omq * logf(q));
+        } else {
+            acc[0] += w * (lse - zt);                 // -log p_t via log-sum-exp (exact for saturated pixels)
+            acc[1] += w;
+            acc[2] += -kFlAlpha * omq * omq * logf(q);
+        }
     }
     float* dst = partial + (size_t)blockIdx.x * (3 + 3 * C);
 #pragma unroll
@@ -131,12 +166,15 @@ typedef float loss_f4 __attribute__((ext_vector_type(4)));
 
 // IGN: inv_n is not used (1 / the valid count of `stats` instead, rounded as the host rounds 1 / n_global for the plain form); skipped
 // pixels write a zero row of Cstore floats -- with 16-byte stores when zero16 (dpitch % 4 == 0 and an aligned base, so Cstore % 4 == 0)
-template <int C, typename TT, bool IGN>
+// PW (needs IGN): a pixel whose weight is not in (0, FLT_MAX] is skipped too; the others' rows are scaled by gs * u
+template <int C, typename TT, bool IGN, bool PW>
 __global__ __launch_bounds__(256) void multiloss_bwd_kernel(const float* __restrict__ logits, int pitch, const TT* __restrict__ target,
                                                             long long N, const float* __restrict__ cw, const float* __restrict__ stats,
                                                             float inv_n, float w_ce, float w_d, float w_f,
                                                             const float* __restrict__ grad_scale, float* __restrict__ dlogits, int dpitch,
-                                                            int Cstore, unsigned* __restrict__ amax_out, long long ignore, int zero16) {
+                                                            int Cstore, unsigned* __restrict__ amax_out, long long ignore, int zero16,
+                                                            const float* __restrict__ pw) {
+    static_assert(IGN || !PW, "pixel weights ride on the ignore path");
     // per-class Dice coefficients: dL_d/dp_c(n) = -[2 o_c (K_c + s) - (2 I_c + s)] / (K_c + s)^2 / C = o_c * A_c + B_c
     float dA[C], dB[C];
 #pragma unroll
@@ -158,8 +196,15 @@ __global__ __launch_bounds__(256) void multiloss_bwd_kernel(const float* __restr
     float gmax = 0.f;                          // max |dlogits|: the range the conv backward that receives them scales its operand with
     for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long long)gridDim.x * blockDim.x) {
         const long long tl = (long long)target[n];
+        float gsu = gs;
+        bool skip_u = false;
+        if constexpr (PW) {
+            const float u = pw[n];
+            skip_u = !(u > 0.f && u <= FLT_MAX);
+            gsu = gs * u;
+        }
         if constexpr (IGN) {
-            if (tl == ignore || (unsigned long long)tl >= (unsigned long long)C) {
+            if (tl == ignore || (unsigned long long)tl >= (unsigned long long)C || skip_u) {
                 float* zrow = dlogits + n * dpitch;
                 if (zero16) {
                     for (int c = 0; c < Cstore; c += 4) *reinterpret_cast<loss_f4*>(zrow + c) = loss_f4{0.f, 0.f, 0.f, 0.f};
@@ -193,8 +238,8 @@ __global__ __launch_bounds__(256) void multiloss_bwd_kernel(const float* __restr
             const float o = (c == t) ? 1.f : 0.f;
             const float gc = (c == t ? dA[c] : 0.f) + dB[c];
             const float d = ce_norm * w * (p[c] - o) + w_d * p[c] * (gc - gdot) + fcoef * (o - p[c]);
-            dst[c] = gs * d;
-            gmax = fmaxf(gmax, fabsf(gs * d));
+            dst[c] = gsu * d;
+            gmax = fmaxf(gmax, fabsf(gsu * d));
         }
         for (int c = C; c < Cstore; ++c) dst[c] = 0.f;     // channel padding up to the pitch stays zero
     }
@@ -211,22 +256,30 @@ extern "C" size_t pylc_multiloss_workspace_floats(long long N, int C) {
 }
 
 static int multiloss_stats_impl(const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N, int C, long long ignore,
-                                const float* cw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
+                                const float* cw, const float* pw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
     hipStream_t st = as_stream(stream);
     const int blocks = (int)(cdiv<long long>(N, 256) < kLossBlocks ? cdiv<long long>(N, 256) : kLossBlocks);
-#define LAUNCH_STATS_T(CC, TT, IGN)                                                                                                          \
-    hipLaunchKernelGGL((multiloss_stats_kernel<CC, TT, IGN>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
-                       workspace, ignore, n_bad)
+#define LAUNCH_STATS_T(CC, TT, IGN, PW)                                                                                                                 \
+    hipLaunchKernelGGL((multiloss_stats_kernel<CC, TT, IGN, PW>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
+                       workspace, ignore, n_bad, pw)
     if (!ign) {
-#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, false)
+#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, false, false)
+        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
+#undef LAUNCH_STATS
+    } else if (pw != nullptr && target_bytes == 8) {
+#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, true, true)
+        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
+#undef LAUNCH_STATS
+    } else if (pw != nullptr) {
+#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, unsigned char, true, true)
         PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
 #undef LAUNCH_STATS
     } else if (target_bytes == 8) {
-#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, true)
+#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, true, false)
         PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
 #undef LAUNCH_STATS
     } else {
-#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, unsigned char, true)
+#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, unsigned char, true, false)
         PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
 #undef LAUNCH_STATS
     }
@@ -242,7 +295,7 @@ extern "C" int pylc_multiloss_stats(const float* logits, int pitch, const int64_
                                     float* workspace, void* stream) {
     PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats: n_classes=%d unsupported (2..%d)", C, MAXC);
     PYLC_REQUIRE(logits && target && stats && workspace && N > 0 && pitch >= C, "multiloss_stats: bad arguments");
-    return multiloss_stats_impl(logits, pitch, target, 8, false, N, C, 0, cw, stats, workspace, nullptr, stream);
+    return multiloss_stats_impl(logits, pitch, target, 8, false, N, C, 0, cw, nullptr, stats, workspace, nullptr, stream);
 }
 
 extern "C" int pylc_multiloss_stats_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
@@ -255,7 +308,24 @@ extern "C" int pylc_multiloss_stats_ex(const float* logits, int pitch, const voi
     PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_ex: logits, stats or workspace is NULL");
     PYLC_REQUIRE((target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0) && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0,
                  "multiloss_stats_ex: a buffer is not aligned to its element");
-    return multiloss_stats_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, stats, workspace, n_bad, stream);
+    return multiloss_stats_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, nullptr, stats, workspace, n_bad, stream);
+}
+
+// pixel_weights == NULL: the very instantiations of _ex
+extern "C" int pylc_multiloss_stats_w(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                                      const float* cw, const float* pixel_weights, float* stats, float* workspace, unsigned long long* n_bad,
+                                      void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats_w: n_classes=%d unsupported (2..%d)", C, MAXC);
+    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_stats_w: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
+    PYLC_REQUIRE(target, "multiloss_stats_w: target is NULL");
+    PYLC_REQUIRE(pitch >= C, "multiloss_stats_w: pitch=%d below n_classes=%d", pitch, C);
+    PYLC_REQUIRE(N > 0, "multiloss_stats_w: N=%lld is not positive", N);
+    PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_w: logits, stats or workspace is NULL");
+    PYLC_REQUIRE((target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0) && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0 &&
+                     (reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0,
+                 "multiloss_stats_w: a buffer is not aligned to its element");
+    return multiloss_stats_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, pixel_weights, stats, workspace, n_bad,
+                                stream);
 }
 
 extern "C" int pylc_multiloss_finalize(const float* stats, double n_global, int C, float w_ce, float w_dice, float w_focal, float* losses,
@@ -275,7 +345,7 @@ extern "C" int pylc_multiloss_finalize_ex(const float* stats, int C, float w_ce,
 }
 
 static int multiloss_bwd_impl(const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N, int C, long long ignore,
-                              const float* cw, const float* stats, double n_global, float w_ce, float w_dice, float w_focal,
+                              const float* cw, const float* pw, const float* stats, double n_global, float w_ce, float w_dice, float w_focal,
                               const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
     hipStream_t st = as_stream(stream);
     if (amax_bits != nullptr) PYLC_HIP(hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st));
@@ -283,19 +353,27 @@ static int multiloss_bwd_impl(const float* logits, int pitch, const void* target
     const int Cstore = ((C + 3) & ~3) <= dpitch ? ((C + 3) & ~3) : C;
     const float inv_n = ign ? 0.f : (float)(1.0 / n_global);
     const int zero16 = dpitch % 4 == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;      // then Cstore = roundup4(C) <= dpitch
-#define LAUNCH_BWD_T(CC, TT, IGN)                                                                                                              \
-    hipLaunchKernelGGL((multiloss_bwd_kernel<CC, TT, IGN>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
-                       stats, inv_n, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, Cstore, amax_bits, ignore, zero16)
+#define LAUNCH_BWD_T(CC, TT, IGN, PW)                                                                                                                 \
+    hipLaunchKernelGGL((multiloss_bwd_kernel<CC, TT, IGN, PW>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
+                       stats, inv_n, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, Cstore, amax_bits, ignore, zero16, pw)
     if (!ign) {
-#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, false)
+#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, false, false)
+        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
+#undef LAUNCH_BWD
+    } else if (pw != nullptr && target_bytes == 8) {
+#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, true, true)
+        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
+#undef LAUNCH_BWD
+    } else if (pw != nullptr) {
+#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, unsigned char, true, true)
         PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
 #undef LAUNCH_BWD
     } else if (target_bytes == 8) {
-#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, true)
+#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, true, false)
         PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
 #undef LAUNCH_BWD
     } else {
-#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, unsigned char, true)
+#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, unsigned char, true, false)
         PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
 #undef LAUNCH_BWD
     }
@@ -309,7 +387,7 @@ extern "C" int pylc_multiloss_bwd(const float* logits, int pitch, const int64_t*
                                   float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
     PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd: n_classes=%d unsupported (2..%d)", C, MAXC);      // before amax_bits is cleared
     PYLC_REQUIRE(logits && target && stats && dlogits && N > 0 && pitch >= C && dpitch >= C && n_global > 0, "multiloss_bwd: bad arguments");
-    return multiloss_bwd_impl(logits, pitch, target, 8, false, N, C, 0, cw, stats, n_global, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch,
+    return multiloss_bwd_impl(logits, pitch, target, 8, false, N, C, 0, cw, nullptr, stats, n_global, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch,
                               amax_bits, stream);
 }
 
@@ -323,6 +401,21 @@ extern "C" int pylc_multiloss_bwd_ex(const float* logits, int pitch, const void*
     PYLC_REQUIRE(N > 0, "multiloss_bwd_ex: N=%lld is not positive", N);
     PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_ex: logits, stats or dlogits is NULL");
     PYLC_REQUIRE(target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0, "multiloss_bwd_ex: an int64 target is not 8-byte aligned");
-    return multiloss_bwd_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, stats, 1.0, w_ce, w_dice, w_focal,
+    return multiloss_bwd_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, nullptr, stats, 1.0, w_ce, w_dice, w_focal,
                               grad_scale, dlogits, dpitch, amax_bits, stream);
+}
+
+extern "C" int pylc_multiloss_bwd_w(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                                    const float* cw, const float* pixel_weights, const float* stats, float w_ce, float w_dice, float w_focal,
+                                    const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd_w: n_classes=%d unsupported (2..%d)", C, MAXC);    // before amax_bits is cleared
+    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_bwd_w: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
+    PYLC_REQUIRE(target, "multiloss_bwd_w: target is NULL");
+    PYLC_REQUIRE(pitch >= C && dpitch >= C, "multiloss_bwd_w: pitch=%d or dpitch=%d below n_classes=%d", pitch, dpitch, C);
+    PYLC_REQUIRE(N > 0, "multiloss_bwd_w: N=%lld is not positive", N);
+    PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_w: logits, stats or dlogits is NULL");
+    PYLC_REQUIRE(target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0, "multiloss_bwd_w: an int64 target is not 8-byte aligned");
+    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0, "multiloss_bwd_w: pixel_weights is not 4-byte aligned");
+    return multiloss_bwd_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, pixel_weights, stats, 1.0, w_ce, w_dice,
+                              w_focal, grad_scale, dlogits, dpitch, amax_bits, stream);
 }

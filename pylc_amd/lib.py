@@ -221,6 +221,8 @@ SIGNATURES = {
     'pylc_boundary_distance': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     'pylc_boundary_counts': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     'pylc_boundary_counts_maps': (_I, [_P, _P, _P, _P, _LL, _I, _I, _I, _P, _P]),
+    'pylc_boundary_weights': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'pylc_weights_from_d2': (_I, [_P, _LL, _I, _P, _P, _P]),
     'pylc_nhwc_to_nchw': (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     'pylc_nchw_to_nhwc': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'pylc_multiloss_workspace_floats': (_SZ, [_LL, _I]),
@@ -230,6 +232,8 @@ SIGNATURES = {
     'pylc_multiloss_stats_ex': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P, _P, _P, _P]),
     'pylc_multiloss_finalize_ex': (_I, [_P, _I, _F, _F, _F, _P, _P]),
     'pylc_multiloss_bwd_ex': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P, _F, _F, _F, _P, _P, _I, _P, _P]),
+    'pylc_multiloss_stats_w': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'pylc_multiloss_bwd_w': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P, _P, _F, _F, _F, _P, _P, _I, _P, _P]),
     'pylc_sqnorm_workspace_floats': (_SZ, [_LL]),
     'pylc_grad_norm_clip': (_I, [_P, _LL, _F, _P, _P, _P]),
     'pylc_adamw_step': (_I, [_P, _P, _P, _P, _LL, _P, _F, _F, _F, _F, _F, _I, _P]),

@@ -15,6 +15,11 @@ class MultiLoss(nn.Module):
     targets may then be uint8 or int64.  Any other target outside 0..n_classes-1 is skipped too and counted in `.bad_targets` (an int64
     [1] device tensor, read by Model.log).
 
+    pixel_weights (every callable's optional third argument; not in the reference): a float32 [B,H,W] device map
+    u_n, one weight per pixel, e.g. boundary.border_weights(target, ...) or a confidence map.  Each term becomes its u-weighted form
+    (CE = sum u w_t nll / sum u w_t, Dice over u-weighted sums, Focal = sum u f / sum u); u_n == 0 leaves the pixel out, negative, NaN
+    and infinite weights are left out and counted in `.bad_targets`.  None: the paths without weights, unchanged.
+
     forward(pred, target) -> 0-d tensor (ce_w*CE + dice_w*Dice + focal_w*Focal) with grad; side effects
     .ce / .dsc / .fl hold the three terms (loss.py:107-112).  One kernel pass computes all three."""
 
@@ -48,33 +53,33 @@ class MultiLoss(nn.Module):
         if pred.device != target.device:
             raise ValueError('input and target must be in the same device. Got: {} and {}'.format(pred.device, target.device))
 
-    def _all(self, pred, target, w_ce, w_d, w_f):
+    def _all(self, pred, target, w_ce, w_d, w_f, pixel_weights=None):
         self._check(pred, target)
         cw = self.weights if self.weighted else None
-        if self.ignore_index is None:
+        if self.ignore_index is None and pixel_weights is None:
             return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group)
         if self.bad_targets is None or self.bad_targets.device != pred.device:
             self.bad_targets = torch.zeros(1, dtype=torch.int64, device=pred.device)
-        return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group, self.ignore_index, self.bad_targets)
+        return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group, self.ignore_index, self.bad_targets, pixel_weights)
 
-    def forward(self, pred, target):
-        losses = self._all(pred, target, self.ce_weight, self.dsc_weight, self.fl_weight)
+    def forward(self, pred, target, pixel_weights=None):
+        losses = self._all(pred, target, self.ce_weight, self.dsc_weight, self.fl_weight, pixel_weights)
         self.ce, self.dsc, self.fl = losses[1].detach(), losses[2].detach(), losses[3].detach()
         return losses[0]
 
     # the validation path calls the three terms separately (model.py:360-362)
-    def ce_loss(self, pred, target):
-        return self._all(pred, target, 1.0, 0.0, 0.0)[0]
+    def ce_loss(self, pred, target, pixel_weights=None):
+        return self._all(pred, target, 1.0, 0.0, 0.0, pixel_weights)[0]
 
-    def dice_loss(self, pred, target):
-        return self._all(pred, target, 0.0, 1.0, 0.0)[0]
+    def dice_loss(self, pred, target, pixel_weights=None):
+        return self._all(pred, target, 0.0, 1.0, 0.0, pixel_weights)[0]
 
-    def focal_loss(self, pred, target):
-        return self._all(pred, target, 0.0, 0.0, 1.0)[0]
+    def focal_loss(self, pred, target, pixel_weights=None):
+        return self._all(pred, target, 0.0, 0.0, 1.0, pixel_weights)[0]
 
-    def all_losses(self, pred, target):
+    def all_losses(self, pred, target, pixel_weights=None):
         """(total, ce, dice, focal) as one [4] tensor from a single pass."""
-        return self._all(pred, target, self.ce_weight, self.dsc_weight, self.fl_weight)
+        return self._all(pred, target, self.ce_weight, self.dsc_weight, self.fl_weight, pixel_weights)
 
     def print_settings(self):
         hline = '_' * 40

@@ -53,6 +53,8 @@ class Meta:
         self.pretrained = False
         self.freeze_bn = False             # fine-tuning: BatchNorms keep their running statistics in training steps (DeepLab(freeze_bn=True))
         self.ignore_index = None           # an int (255 for uint8 masks): pixels with this label are left out of the loss and the scores
+        self.border_weight = None          # None, or {'w0':, 'sigma':, 'radius':}: training weighs a pixel by 1 + w0 exp(-d^2 / (2 sigma^2)) of its
+        #                                    distance d to the nearest pixel of another class within `radius` (boundary.border_profile)
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise AttributeError('unknown Meta field %r' % k)
@@ -159,6 +161,7 @@ class Model:
         self.scores = None                  # a metrics.ScoreLog: Model.eval also counts the confusion matrix, Model.log closes the pass
         self._best_by = 'dice'
         self._ranges_checked = False        # eval / test: False until the first batch after a training step has re-measured the weight ranges
+        self._border = None                 # (radius, ignore value of the distance pass, device table) of Meta.border_weight, set by build()
 
     @property
     def best_by(self):
@@ -199,8 +202,39 @@ class Model:
         ign = None if m.ignore_index is None else int(m.ignore_index)
         if self.scores is not None and self.scores.ignore_index != ign:
             self.scores.ignore_index, self.scores.counts = ign, None          # (the counts gain or lose the cell of the ignored pixels)
+        self._border = self._border_table(m)
         self.init_optim()
         return self
+
+    def _border_table(self, m):
+        """Meta.border_weight -> (radius, ignore_index or None, the profile as a device tensor, put there once), or None."""
+        bw = getattr(m, 'border_weight', None)
+        if bw is None:
+            return None
+        from . import boundary
+        if not isinstance(bw, dict) or set(bw) != {'w0', 'sigma', 'radius'}:
+            raise ValueError("Meta.border_weight is None or {'w0':, 'sigma':, 'radius':}, got %r" % (bw,))
+        if m.ignore_index is not None and not 0 <= int(m.ignore_index) <= 255:
+            raise ValueError('border_weight takes the distances of uint8 masks: ignore_index=%d does not fit one (0..255)' % int(m.ignore_index))
+        table = boundary.border_profile(bw['radius'], bw['w0'], bw['sigma'])
+        return int(bw['radius']), m.ignore_index, torch.from_numpy(table).to(self.device)
+
+    def _train_weights(self, y, pixel_weights):
+        """The weight map of a training step, or None: Meta.border_weight's map of the cropped target y (the tile's edge is no border; an
+        int64 target is converted to uint8 for the distance pass only), times the caller's map cropped like the target."""
+        u = None
+        if pixel_weights is not None:
+            if not torch.is_tensor(pixel_weights) or pixel_weights.dim() != 3:
+                raise ValueError('pixel_weights must be a [B,H,W] tensor')
+            u = self.crop_target(pixel_weights.to(self.device, non_blocking=True).float())
+            if tuple(u.shape) != tuple(y.shape):
+                raise ValueError('pixel_weights %s do not match the target %s' % (tuple(pixel_weights.shape), tuple(y.shape)))
+        if self._border is not None:
+            from . import boundary
+            radius, ign, table = self._border
+            border = boundary.border_weights(y if y.dtype == torch.uint8 else y.to(torch.uint8), radius, table, ignore_index=ign)
+            u = border if u is None else torch.mul(border, u)
+        return u
 
     def init_optim(self):
         """model.py:238-280.  Call again after load_state_dict() into self.net is NOT needed: the arena aliases
@@ -253,8 +287,10 @@ class Model:
         return y.contiguous()
 
     # ---- the three hot-path entry points ---------------------------------------------------------------------
-    def train(self, x, y):
-        """One optimisation step (model.py:282-336)."""
+    def train(self, x, y, pixel_weights=None):
+        """One optimisation step (model.py:282-336).  pixel_weights (not in the reference): a float [B,H,W] map of the tiles' size, one
+        weight per pixel of the loss (a confidence map, say); it is cropped like the target and multiplied into Meta.border_weight's map
+        where that is set.  Model.eval stays unweighted: validation losses remain comparable between runs."""
         self.net.train()       # (parameter ranges / prepared filters are current: refreshed by every optimiser step and state load)
         if getattr(self.net, 'freeze_bn', False) and ops.nplanes() == 1:
             raise ValueError('freeze_bn is not available in conv precision mode 3: its half activations are scaled with range bounds '
@@ -262,8 +298,9 @@ class Model:
         self._ranges_checked = False
         x4 = self.pack_input(x)
         y = self._target(y)
+        u = self._train_weights(y, pixel_weights)          # None without Meta.border_weight and without a map: the step as it was
         y_hat = self.net(x4)
-        loss = self.crit(y_hat, y)
+        loss = self.crit(y_hat, y) if u is None else self.crit(y_hat, y, u)
         self.loss.push(torch.stack((self.crit.ce, self.crit.dsc, self.crit.fl)))
         self.optim.zero_grad()
         if runtime.sync_group is not None:
@@ -338,6 +375,9 @@ class Model:
             n_bad = int(bad.item())
             if n_bad:
                 bad.zero_()
+                if self.meta.ignore_index is None:      # (the counter exists without an index only where pixel weights were given)
+                    raise ValueError('%d pixels since the last report hold a target outside 0..%d or a negative, NaN or infinite weight'
+                                     % (n_bad, self.meta.n_classes - 1))
                 raise ValueError('%d targets since the last report lie outside 0..%d and are not ignore_index=%d'
                                  % (n_bad, self.meta.n_classes - 1, self.meta.ignore_index))
         if self._best_by == 'iou' and self.scores is None:

@@ -447,18 +447,33 @@ class MultiLossFn(torch.autograd.Function):
     ignore_index (an int; None: the plain path): targets may be uint8 or int64, pixels whose target equals the index or lies outside
     0..C-1 are skipped (pylc_multiloss_*_ex) and the number of valid pixels is read on the device from the
     (all-reduced) statistics.  bad: an int64 [1] device tensor that the number of out-of-range targets other than the index is ADDED
-    into (optional)."""
+    into (optional).
+
+    pixel_weights (float32 [B,H,W] on the logits' device; None: the paths above, untouched): a weight u_n per pixel (pylc_multiloss_*_w,
+    DESIGN.md section 5.16) -- a saved tensor, no gradient flows into it.  A pixel with u_n == 0 is skipped like an ignored one; negative,
+    NaN and infinite weights are skipped and counted in `bad`.  Without an ignore_index the kernels get INT32_MIN as the ignore value, which
+    no uint8 target and no class index equals."""
+
+    NO_IGNORE = -2 ** 31
 
     @staticmethod
-    def forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index=None, bad=None):
+    def forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index=None, bad=None, pixel_weights=None):
         L.init()
         logits = as_nhwc(logits)
         b, c, h, w = logits.shape
         n = b * h * w
         target = target.contiguous()
+        if pixel_weights is not None:
+            if (not torch.is_tensor(pixel_weights) or pixel_weights.dtype != torch.float32 or tuple(pixel_weights.shape) != (b, h, w)
+                    or pixel_weights.device != logits.device):
+                raise L.PylcError('pixel_weights must be float32 [B,H,W] matching the logits, on their device')
+            pixel_weights = pixel_weights.detach().contiguous()
+            if ignore_index is None:
+                ignore_index = MultiLossFn.NO_IGNORE
         ctx.ignore = ignore_index
         if ignore_index is not None:
-            return MultiLossFn._forward_ignore(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, int(ignore_index), bad)
+            return MultiLossFn._forward_ignore(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, int(ignore_index), bad,
+                                               pixel_weights)
         if target.dtype != torch.int64 or tuple(target.shape) != (b, h, w):
             raise L.PylcError('target must be int64 [B,H,W] matching the logits')
         dev = logits.device
@@ -484,7 +499,7 @@ class MultiLossFn(torch.autograd.Function):
         return losses
 
     @staticmethod
-    def _forward_ignore(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad):
+    def _forward_ignore(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights=None):
         b, c, h, w = logits.shape
         n = b * h * w
         if target.dtype not in (torch.uint8, torch.int64) or tuple(target.shape) != (b, h, w):
@@ -496,21 +511,30 @@ class MultiLossFn(torch.autograd.Function):
         k = 3 + 3 * c
         stats = torch.empty(k + (2 if group is not None else 0), device=dev)         # (the shard pair rides along as on the plain path)
         ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
-        check(lib.pylc_multiloss_stats_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
-                                          ptr(class_weights), ptr(stats), ptr(ws), ptr(bad), st))
+        if pixel_weights is None:
+            check(lib.pylc_multiloss_stats_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
+                                              ptr(class_weights), ptr(stats), ptr(ws), ptr(bad), st))
+        else:
+            check(lib.pylc_multiloss_stats_w(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
+                                             ptr(class_weights), ptr(pixel_weights), ptr(stats), ptr(ws), ptr(bad), st))
         if group is not None:
             stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
             _runtime.sync_all_reduce(stats, group)
             note_shard_pair(stats[k:], dist.get_world_size(group))
         losses = torch.empty(4, device=dev)
-        check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))      # n_valid: from the reduced class counts
-        ctx.save_for_backward(logits, target, stats, class_weights)
+        check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))      # n_valid (sum u): from the reduced class counts
+        if pixel_weights is None:
+            ctx.save_for_backward(logits, target, stats, class_weights)
+        else:
+            ctx.save_for_backward(logits, target, stats, class_weights, pixel_weights)
         ctx.cfg = (None, w_ce, w_dice, w_focal, group)
         return losses
 
     @staticmethod
     def backward(ctx, dlosses):
-        logits, target, stats, cw = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        logits, target, stats, cw = saved[:4]
+        pw = saved[4] if len(saved) > 4 else None
         n_global, w_ce, w_dice, w_focal, group = ctx.cfg
         b, c, h, w = logits.shape
         n = b * h * w
@@ -524,16 +548,19 @@ class MultiLossFn(torch.autograd.Function):
         if ignore is None:
             check(lib.pylc_multiloss_bwd(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(cw), ptr(stats), n_global,
                                          w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
-        else:
+        elif pw is None:
             check(lib.pylc_multiloss_bwd_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw),
                                             ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
+        else:
+            check(lib.pylc_multiloss_bwd_w(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw),
+                                           ptr(pw), ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
         if amax is not None:
             tag_amax(dl, amax)              # (read by a conv backward directly when the net has no logits up-sampling: the U-Net)
-        return dl, None, None, None, None, None, None, None, None
+        return dl, None, None, None, None, None, None, None, None, None
 
 
-def multiloss(logits, target, class_weights, w_ce, w_dice, w_focal, group=None, ignore_index=None, bad=None):
-    return MultiLossFn.apply(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad)
+def multiloss(logits, target, class_weights, w_ce, w_dice, w_focal, group=None, ignore_index=None, bad=None, pixel_weights=None):
+    return MultiLossFn.apply(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights)
 
 
 __all__ = [n for n in dir() if not n.startswith('__')]      # everything, underscore helpers included: the package re-exports it (pylc_amd/ops/__init__.py)

@@ -477,6 +477,54 @@ def _mli_bwd(ctx, dlosses, _dstats, _dbad):
 torch.library.register_autograd('pylc_hip::multiloss_ignore', _mli_bwd, setup_context=_mli_setup)
 
 
+# The same with a weight per pixel (not in the reference): pixel_weights float32 [B,H,W]; ignore_index may be None.
+# Returns (losses, stats, bad): bad counts the skipped pixels that are neither ignored nor of weight zero (a target out of range, a
+# negative, NaN or infinite weight).  No gradient flows into the weights.
+@torch.library.custom_op('pylc_hip::multiloss_weighted', mutates_args=())
+def multiloss_weighted(logits: Tensor, target: Tensor, pixel_weights: Tensor, class_weights: Optional[Tensor], w_ce: float, w_dice: float,
+                       w_focal: float, ignore_index: Optional[int]) -> Tuple[Tensor, Tensor, Tensor]:
+    ctx = _Ctx((True,))
+    bad = torch.zeros(1, dtype=torch.int64, device=logits.device)
+    losses = ops.MultiLossFn.forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, None, ignore_index, bad, pixel_weights)
+    return losses, ctx.saved_tensors[2], bad
+
+
+@multiloss_weighted.register_fake
+def _(logits, target, pixel_weights, class_weights, w_ce, w_dice, w_focal, ignore_index):
+    return logits.new_empty(4), logits.new_empty(3 + 3 * logits.shape[1]), logits.new_empty(1, dtype=torch.int64)
+
+
+@torch.library.custom_op('pylc_hip::multiloss_weighted_backward', mutates_args=())
+def multiloss_weighted_backward(dlosses: Tensor, logits: Tensor, target: Tensor, pixel_weights: Tensor, stats: Tensor,
+                                class_weights: Optional[Tensor], w_ce: float, w_dice: float, w_focal: float,
+                                ignore_index: Optional[int]) -> Tensor:
+    ctx = _Ctx((True,))
+    ctx.save_for_backward(ops.as_nhwc(logits), target.contiguous(), stats, class_weights, pixel_weights.contiguous())
+    ctx.cfg = (None, w_ce, w_dice, w_focal, None)
+    ctx.ignore = ops.MultiLossFn.NO_IGNORE if ignore_index is None else ignore_index
+    return ops.MultiLossFn.backward(ctx, dlosses)[0]
+
+
+@multiloss_weighted_backward.register_fake
+def _(dlosses, logits, target, pixel_weights, stats, class_weights, w_ce, w_dice, w_focal, ignore_index):
+    return torch.empty_like(logits)
+
+
+def _mlw_setup(ctx, inputs, output):
+    logits, target, pw, cw, w_ce, w_dice, w_focal, ignore_index = inputs
+    ctx.save_for_backward(logits, target, pw, output[1], cw)
+    ctx.w = (w_ce, w_dice, w_focal, ignore_index)
+
+
+def _mlw_bwd(ctx, dlosses, _dstats, _dbad):
+    logits, target, pw, stats, cw = ctx.saved_tensors
+    return (torch.ops.pylc_hip.multiloss_weighted_backward(dlosses, logits, target, pw, stats, cw, *ctx.w), None, None, None, None, None, None,
+            None)
+
+
+torch.library.register_autograd('pylc_hip::multiloss_weighted', _mlw_bwd, setup_context=_mlw_setup)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # input normalisation (Model.normalize_image, models/model.py:416-445, + the x3 channel stack :310-311) -> NHWC4 network input
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -493,4 +541,4 @@ def _(img, mean, std):
 REGISTERED = ('conv2d', 'conv2d_backward', 'dwconv3x3', 'dwconv3x3_backward', 'batch_norm_act', 'batch_norm_act_backward', 'relu',
               'relu_backward', 'max_pool2d', 'max_pool2d_backward', 'bilinear', 'bilinear_backward', 'global_avg_pool',
               'global_avg_pool_backward', 'dropout', 'multiloss', 'multiloss_backward', 'multiloss_ignore', 'multiloss_ignore_backward',
-              'image_pack')
+              'image_pack', 'multiloss_weighted', 'multiloss_weighted_backward')
