@@ -99,9 +99,12 @@ typedef struct PylcConvDesc {
  *   2 = "f16x3": each fp32 operand is scaled by an exact power of two taken from the tensor's max magnitude
  *       (PylcConvDesc.*_amax) and split into two fp16 pieces h0 = rn(s*x), h1 = rn(2^11 (s*x - h0)); a product is
  *       a0b0 + 2^-11 (a1b0 + a0b1) on v_mfma_f32_32x32x16_f16, the cross terms in their own fp32 accumulator (the
- *       single-precision-recovery scheme of Ootomo & Yokota, IJHPCA 2022, moved to CDNA4).  Operand error <= 2^-23 |x|
- *       for every element within 2^29 of the tensor maximum (fp16 subnormals are honoured by the MFMA, measured), the
- *       dropped a1b1 term <= 2^-22 |ab|; measured error vs fp64 is below the fp32 chain's.  3 MFMAs instead of 6. */
+ *       single-precision-recovery scheme of Ootomo & Yokota, IJHPCA 2022, moved to CDNA4).  Operand error
+ *       |h0 + 2^-11 h1 - s x| / s <= max(2^-23 |x|, 2^-36 / s): 2^-23 relative for every element with |s x| >= 2^-13, i.e.
+ *       |x| >= 2^-27 of the range bound (the bound maps into [2^14, 2^15)), and absolute 2^-36 / s below that -- 2^-50 ..
+ *       2^-51 of the bound (fp16 subnormals are kept by the conversions and honoured by the MFMA, measured; derivation and
+ *       bit-exact model: tests/_planes.py).  The dropped a1b1 term <= 2^-22 |ab|; measured error vs fp64 is below the fp32
+ *       chain's.  3 MFMAs instead of 6. */
 int pylc_set_conv_precision(int mode);
 int pylc_get_conv_precision(void);
 
@@ -135,7 +138,7 @@ int pylc_weight_prepare(const float* base, const PylcWPrepEntry* table, int coun
                         const unsigned int* amax, void* planes, int interleave, void* stream);
 /* out = bits(factor * float(a) * float(b) [+ float(add)]): a range BOUND for a tensor that is bilinear in two ranged operands -- a depthwise
  * 3x3 output, |y| <= 9 max|w| max|x|; a conv output with bias, |y| <= Cin R S max|w| max|x| + max|bias| (add_bits, may be NULL) -- instead of
- * a read pass over it (the f16x3 arithmetic needs a float >= max|element| within 2^29 of the small elements that matter, not the maximum) */
+ * a read pass over it (the f16x3 arithmetic needs a float >= max|element| within 2^27 of the small elements that matter, not the maximum) */
 int pylc_range_product(const unsigned int* a_bits, const unsigned int* b_bits, float factor, const unsigned int* add_bits,
                        unsigned int* out_bits, void* stream);
 int pylc_amax_segments(const float* base, const long long* offsets, int count, unsigned int* out_bits, void* stream);
@@ -145,6 +148,9 @@ int pylc_amax_segments(const float* base, const long long* offsets, int count, u
  * s the power of two that maps the bound behind `amax` into [2^14, 2^15) -- the two pieces the f16x3 arithmetic forms from an
  * fp32 operand, written ONCE by the tensor's producer (4 bytes per element, like fp32) so that the conv kernels copy operand
  * tiles to LDS by LDS-DMA with no arithmetic.  nplanes = 1 writes / reads plane 0 only (precision mode 3).
+ * The scale rule: exponent field of s = 127 + 14 - (e - 127), e the exponent field of the bound, clamped to 1..242 (s <= 2^115) -- ONE
+ * definition (csrc/common.h pow2_scale_for) for every writer and reader of fp16 pieces, two planes or one.  rn16 rounds to nearest even and
+ * keeps subnormals; every nonzero piece is exactly as stated, the SIGN of a zero piece is unspecified (for x = -0 plane 1 may hold -0).
  * Replaces nothing in the reference: it is the HBM layout of the activations between the BatchNorm and conv kernels. */
 /* Chunk-interleaved two-plane tensors (round 5).  `plane_stride == 32` in any of the entry points below (and in PylcBnExtra, pylc_maxpool_fwd_planes,
  * pylc_gap_fwd_planes, ...) says: flat element e of the dense [M][C] tensor (C % 32 == 0) is at halves (e >> 5) * 64 + (e & 31) for plane 0 and

@@ -174,8 +174,8 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
     }
     float gmax = 0.f;
     float a_inv = 1.f, y_inv = 1.f;
-    if constexpr (AH) a_inv = 1.f / half_scale_for(*ex.dout_bound);
-    if constexpr (YH) y_inv = 1.f / half_scale_for(*ex.y_bound);
+    if constexpr (AH) a_inv = 1.f / pow2_scale_for(*ex.dout_bound);
+    if constexpr (YH) y_inv = 1.f / pow2_scale_for(*ex.y_bound);
     for (int cb = 0; cb < g.CV; cb += g.cols) {
         const int cv = cb + tx;
         const bool active = ty < g.RL && cv < g.CV;
@@ -512,7 +512,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     }
     const bool res_pl = EX && pr.base != nullptr, out_pl = EX && po.base != nullptr;
     float y_inv = 1.f;
-    if constexpr (YH) y_inv = 1.f / half_scale_for(*ex.y_bound);
+    if constexpr (YH) y_inv = 1.f / pow2_scale_for(*ex.y_bound);
     if (ty < g.RL) {
         for (int cv = tx; cv < g.CV; cv += g.cols) {
             const f32x4 sc = ld4(scale + 4 * cv), sh = ld4(shift + 4 * cv);
@@ -610,8 +610,8 @@ __global__ __launch_bounds__(256, TWIN ? 2 : 3) void bn_bwd_apply_kernel(const f
     [[maybe_unused]] float amax2 = 0.f;
     if constexpr (TWIN) { if (tw.dy_pl != nullptr) pd2 = PlanesRef{tw.dy_pl, tw.dy_ps, ex.nplanes, pow2_scale_for(*tw.dy_bound)}; }
     float a_inv = 1.f, y_inv = 1.f, g_scale = 1.f;
-    if constexpr (AH) { a_inv = 1.f / half_scale_for(*ex.dout_bound); g_scale = half_scale_for(*ex.dout_bound); }
-    if constexpr (YH) y_inv = 1.f / half_scale_for(*ex.y_bound);
+    if constexpr (AH) { a_inv = 1.f / pow2_scale_for(*ex.dout_bound); g_scale = pow2_scale_for(*ex.dout_bound); }
+    if constexpr (YH) y_inv = 1.f / pow2_scale_for(*ex.y_bound);
     if (ty < g.RL) {
         for (int cv = tx; cv < g.CV; cv += g.cols) {
             const f32x4 mu = ld4(mean + 4 * cv), is = ld4(invstd + 4 * cv);

@@ -65,6 +65,18 @@ inline long long planes_stride_rule(long long M, int C, int pitch, int nplanes) 
     return il ? kPlanesIL : M * pitch;
 }
 
+// THE scale rule (one place): the power of two that maps a tensor with max magnitude `amax` (given as float bits) into [2^14, 2^15) --
+// exact to apply and to undo, keeps the fp16 pieces clear of overflow with the low piece inside the (sub)normal range for 40 binades.
+// Every writer and reader of fp16 pieces, two planes or one, takes its scale from here.
+// The scale stops at 2^115 (a bound below 2^-101, an all-zero tensor included -- the gradient of a batch without a labelled pixel,
+// DESIGN.md section 5.9): the two-piece split multiplies it by 2^11, and 2^127 * 2^11 = inf would turn every zero into 0 * inf = NaN.
+__device__ __forceinline__ float pow2_scale_for(unsigned amax_bits) {
+    int e = (int)((amax_bits >> 23) & 0xFFu);                  // biased exponent of amax (0: zero / denormal)
+    int se = 127 + 14 - (e - 127);
+    se = se < 1 ? 1 : (se > 242 ? 242 : se);
+    return __uint_as_float((unsigned)se << 23);
+}
+
 constexpr int kWave = 64;
 constexpr int kNumCU = 256;
 

@@ -54,16 +54,7 @@ __device__ __forceinline__ void split2(const f32x4 v, float s, uint2& p0, uint2&
     p1.x = __builtin_bit_cast(unsigned, l1); p1.y = __builtin_bit_cast(unsigned, h1);
 }
 
-// power-of-two scale that maps a tensor with max magnitude `amax` (given as float bits) into [2^14, 2^15): exact to apply
-// and to undo, keeps the fp16 pieces clear of overflow with the low piece inside the (sub)normal range for 40 binades.
-// The scale stops at 2^115 (a bound below 2^-101, an all-zero tensor included -- the gradient of a batch without a labelled pixel,
-// DESIGN.md section 5.9): split2 multiplies it by 2^11, and 2^127 * 2^11 = inf would turn every zero into 0 * inf = NaN.
-__device__ __forceinline__ float pow2_scale_for(unsigned amax_bits) {
-    int e = (int)((amax_bits >> 23) & 0xFFu);                  // biased exponent of amax (0: zero / denormal)
-    int se = 127 + 14 - (e - 127);
-    se = se < 1 ? 1 : (se > 242 ? 242 : se);
-    return __uint_as_float((unsigned)se << 23);
-}
+// (the power-of-two scale of a range bound: common.h pow2_scale_for)
 
 // 1 / s for a power of two s in [2^-126, 2^127] by exponent arithmetic (2^-127 is the subnormal 0x00400000)
 __device__ __forceinline__ float pow2_inv(float s) {

@@ -193,13 +193,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
     const int s_end = s_begin + s.strips_per_block < s.n_strips ? s_begin + s.strips_per_block : s.n_strips;
     float in_inv = 1.f, aux_inv = 1.f, out_scale = 1.f, acc_inv = 1.f;
     if constexpr (HIN) {
-        in_inv = 1.f / half_scale_for(*hf.in_bound);
-        if (MODE == 2) aux_inv = 1.f / half_scale_for(*hf.aux_bound);
+        in_inv = 1.f / pow2_scale_for(*hf.in_bound);
+        if (MODE == 2) aux_inv = 1.f / pow2_scale_for(*hf.aux_bound);
     }
     if constexpr (HOUT && MODE != 2) {
         float b = 9.f * __uint_as_float(*hf.w_amax) * __uint_as_float(*(hf.in_true != nullptr ? hf.in_true : hf.in_bound));
-        if (MODE == 1 && accumulate) { b += __uint_as_float(*hf.acc_bound); acc_inv = 1.f / half_scale_for(*hf.acc_bound); }
-        out_scale = half_scale_for(__float_as_uint(b));
+        if (MODE == 1 && accumulate) { b += __uint_as_float(*hf.acc_bound); acc_inv = 1.f / pow2_scale_for(*hf.acc_bound); }
+        out_scale = pow2_scale_for(__float_as_uint(b));
         if (blockIdx.x == 0 && threadIdx.x == 0) *hf.out_bound = __float_as_uint(b);
     }
     const float* const auxf = static_cast<const float*>(aux);
@@ -484,13 +484,13 @@ __global__ __launch_bounds__(256) void dw_tile_kernel(const void* __restrict__ i
     const int q = tid & 31, pt = tid >> 5;
     const int cq = c0 + 4 * q;                              // this thread's 4 channels
     const bool c_ok = cq < d.C;
-    const float in_inv = 1.f / half_scale_for(*hf.in_bound);
+    const float in_inv = 1.f / pow2_scale_for(*hf.in_bound);
     float aux_inv = 1.f, out_scale = 1.f, acc_inv = 1.f;
-    if (MODE == 2) aux_inv = 1.f / half_scale_for(*hf.aux_bound);
+    if (MODE == 2) aux_inv = 1.f / pow2_scale_for(*hf.aux_bound);
     if constexpr (HOUT && MODE != 2) {
         float b = 9.f * __uint_as_float(*hf.w_amax) * __uint_as_float(*(hf.in_true != nullptr ? hf.in_true : hf.in_bound));
-        if (MODE == 1 && accumulate) { b += __uint_as_float(*hf.acc_bound); acc_inv = 1.f / half_scale_for(*hf.acc_bound); }
-        out_scale = half_scale_for(__float_as_uint(b));
+        if (MODE == 1 && accumulate) { b += __uint_as_float(*hf.acc_bound); acc_inv = 1.f / pow2_scale_for(*hf.acc_bound); }
+        out_scale = pow2_scale_for(__float_as_uint(b));
         if (blockIdx.x == 0 && threadIdx.x == 0) *hf.out_bound = __float_as_uint(b);
     }
     f32x4 k[9];                                             // filter taps (MODE 0 / 1, dgrad: flipped) or accumulators (MODE 2)
@@ -538,7 +538,7 @@ __global__ __launch_bounds__(256) void dw_tile_kernel(const void* __restrict__ i
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (MODE != 1 && hf.in_scale != nullptr)
-            dw_bn_patch(lin, DT_PIX, DT_IW, h0 - 1, w0 - 1, d.H, d.W, c0, d.C, hf, 1.f / half_scale_for(*hf.y_bound), half_scale_for(*hf.in_bound));
+            dw_bn_patch(lin, DT_PIX, DT_IW, h0 - 1, w0 - 1, d.H, d.W, c0, d.C, hf, 1.f / pow2_scale_for(*hf.y_bound), pow2_scale_for(*hf.in_bound));
 
         const char* const pin = lin + (2 * pt) * DT_PIXB + q * 8;
         f32x4 win[3][4];
@@ -627,13 +627,13 @@ __global__ __launch_bounds__(256) void dw_tileg_kernel(const void* __restrict__ 
     // geometry of the tensor read through LDS (SH x SW) and of the one written / tiled (DH x DW)
     const int SH = MODE == 1 ? d.OH : d.H, SW = MODE == 1 ? d.OW : d.W;
     const int DH = MODE == 1 ? d.H : d.OH, DW_ = MODE == 1 ? d.W : d.OW;
-    const float in_inv = 1.f / half_scale_for(*hf.in_bound);
+    const float in_inv = 1.f / pow2_scale_for(*hf.in_bound);
     float aux_inv = 1.f, out_scale = 1.f, acc_inv = 1.f;
-    if (MODE == 2) aux_inv = 1.f / half_scale_for(*hf.aux_bound);
+    if (MODE == 2) aux_inv = 1.f / pow2_scale_for(*hf.aux_bound);
     if constexpr (HOUT && MODE != 2) {
         float b = 9.f * __uint_as_float(*hf.w_amax) * __uint_as_float(*(hf.in_true != nullptr ? hf.in_true : hf.in_bound));
-        if (MODE == 1 && accumulate) { b += __uint_as_float(*hf.acc_bound); acc_inv = 1.f / half_scale_for(*hf.acc_bound); }
-        out_scale = half_scale_for(__float_as_uint(b));
+        if (MODE == 1 && accumulate) { b += __uint_as_float(*hf.acc_bound); acc_inv = 1.f / pow2_scale_for(*hf.acc_bound); }
+        out_scale = pow2_scale_for(__float_as_uint(b));
         if (blockIdx.x == 0 && threadIdx.x == 0) *hf.out_bound = __float_as_uint(b);
     }
     f32x4 k[9];
@@ -684,7 +684,7 @@ __global__ __launch_bounds__(256) void dw_tileg_kernel(const void* __restrict__ 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (MODE != 1 && hf.in_scale != nullptr)
-            dw_bn_patch(lin, NPX, PW, ph0, pw0, SH, SW, c0, d.C, hf, 1.f / half_scale_for(*hf.y_bound), half_scale_for(*hf.in_bound));
+            dw_bn_patch(lin, NPX, PW, ph0, pw0, SH, SW, c0, d.C, hf, 1.f / pow2_scale_for(*hf.y_bound), pow2_scale_for(*hf.in_bound));
 
         const char* const pin = lin + q * 8;
         auto px = [&](int iy, int ix) { return half4_to_f32(*reinterpret_cast<const uint2*>(pin + (iy * PW + ix) * DT_PIXB)); };

@@ -22,12 +22,6 @@ static inline int grid_for(long long n, int cap = 8192) {
 // planes != NULL: the pooled tensor leaves as fp16 planes ([nplanes][pixels][C] halves: plane 0 = rn16(sc v), plane 1 = rn16(2^11 (sc v -
 // plane 0)), sc from `bound` -- planes.hip) for a conv that copies its operand tiles, instead of fp32 + a conversion pass.
 struct PoolPlanes { _Float16* planes; long long plane_stride; const unsigned* bound; int nplanes; };
-__device__ __forceinline__ float pool_pow2_scale(unsigned bits) {      // conv_common.h pow2_scale_for: bound -> [2^14, 2^15)
-    int e = (int)((bits >> 23) & 0xFFu);
-    int se = 127 + 14 - (e - 127);
-    se = se < 1 ? 1 : (se > 242 ? 242 : se);
-    return __uint_as_float((unsigned)se << 23);
-}
 
 __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ idx, int B, int H, int W,
                                    int C, int k, int s, int pad, int OH, int OW, PoolPlanes pp) {
@@ -60,7 +54,7 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restric
         }
         if (pp.planes != nullptr) {
             typedef _Float16 f16x4_ __attribute__((ext_vector_type(4)));
-            const float sc = pool_pow2_scale(*pp.bound);
+            const float sc = pow2_scale_for(*pp.bound);
             const f32x4 xs = best * sc;
             const f16x4_ h0 = {(_Float16)xs.x, (_Float16)xs.y, (_Float16)xs.z, (_Float16)xs.w};
             const long long pe = planes_phys(4 * i, pp.nplanes == 2 && planes_il(pp.plane_stride));      // (chunk-interleaved: common.h)
@@ -350,10 +344,7 @@ __global__ __launch_bounds__(256) void gap_fwd_planes_kernel(const _Float16* __r
     const int b = blockIdx.y;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int cv = blockIdx.x * 16 + tx;
-    int e = (int)((*amax >> 23) & 0xFFu);                      // 1 / (the power-of-two scale of the tensor's range bound): conv_common.h pow2_scale_for
-    int se = 127 + 14 - (e - 127);
-    se = se < 1 ? 1 : (se > 242 ? 242 : se);
-    const float inv = 1.f / __uint_as_float((unsigned)se << 23);
+    const float inv = 1.f / pow2_scale_for(*amax);
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
     if (cv < CV) {
         const bool il = NPL == 2 && planes_il(plane_stride);      // chunk-interleaved (common.h): C % 32 == 0, a row starts a chunk

@@ -113,12 +113,6 @@ __device__ __forceinline__ void stq(void* base, size_t elem, f32x4 v, float scal
     if constexpr (HALF) *reinterpret_cast<uint2*>(static_cast<_Float16*>(base) + elem) = f32_to_half4(v * scale);
     else st4(static_cast<float*>(base) + elem, v);
 }
-// the power of two that maps a tensor bounded by `bound_bits` (float bits) into [2^14, 2^15) (conv_common.h pow2_scale_for)
-__device__ __forceinline__ float half_scale_for(unsigned bound_bits) {
-    int e = (int)((bound_bits >> 23) & 0xFFu);
-    int se = 127 + 14 - (e - 127);
-    se = se < 1 ? 1 : (se > 254 ? 254 : se);
-    return __uint_as_float((unsigned)se << 23);
-}
+// (the scale of a one-plane tensor is the one rule of every fp16 piece: common.h pow2_scale_for)
 
 }  // namespace pylc

@@ -8,13 +8,6 @@ namespace pylc {
 
 typedef _Float16 f16;
 
-__device__ __forceinline__ float wprep_scale(unsigned amax_bits) {      // = conv_igemm.hip pow2_scale_for
-    int e = (int)((amax_bits >> 23) & 0xFFu);
-    int se = 127 + 14 - (e - 127);
-    se = se < 1 ? 1 : (se > 242 ? 242 : se);
-    return __uint_as_float((unsigned)se << 23);
-}
-
 __device__ __forceinline__ void wsplit(float w, float s, f16& h0, f16& h1) {
     const float xs = w * s;
     h0 = (f16)xs;
@@ -37,7 +30,7 @@ __global__ __launch_bounds__(256) void weight_prepare_kernel(const float* __rest
         if (table[mid].tile_begin <= tile) lo = mid; else hi = mid - 1;
     }
     const PylcWPrepEntry e = table[lo];
-    const float s = wprep_scale(amax[e.amax_index]);
+    const float s = pow2_scale_for(amax[e.amax_index]);
     const int Kp = (e.K + 3) & ~3;
     const int tk = (e.K + 31) / 32, tc = (e.C + 31) / 32;
     int id = (int)(tile - e.tile_begin);

@@ -647,7 +647,7 @@ def amax_of(t):
 def bound_conv_output(y, x, w, bias=None):
     """Tags the output y of a conv (no BatchNorm behind it) with the range BOUND Cin R S max|w| max|x| + max|bias| (pylc_range_product) when
     x's range is known without a pass (fp16 planes or a valid tag) and the filter's is in the arena table: the U-Net's 1x1 up convs, whose
-    output only the interpolation + concat kernel reads.  The bound is loose by ~log2(sqrt(Cin)) + 3 binades, well inside the 2^29 the split
+    output only the interpolation + concat kernel reads.  The bound is loose by ~log2(sqrt(Cin)) + 3 binades, well inside the 2^27 the split
     arithmetic tolerates (include/pylc_hip.h, precision mode 2).  Returns y."""
     if not (ranges_needed() and _runtime.fused_grad_ranges) or is_planes(y):
         return y

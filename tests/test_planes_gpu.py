@@ -664,3 +664,64 @@ def test_256_row_planes_kernel_is_bit_identical(dev, f16x3, case):
         lib.pylc_debug_pp_flags(0)
     for name in ('256', '256-lockstep'):
         assert torch.equal(out[name][0], out['128'][0]) and torch.equal(out[name][1], out['128'][1]), name
+
+
+def test_conv_on_planes_dynamic_range_per_pixel(dev, f16x3):
+    """The plane-operand form of tests/test_ops_gpu.py::test_conv_f16x3_dynamic_range (there: fp32 operands split inside the kernel, forward
+    only): the same data -- pixel magnitudes from 1 down to 1e-14, 1x1 conv 256 -> 128 on 32 x 32 -- with x converted by ops.to_planes and read
+    by the planes kernel, and the 1x1 data gradient of a dy built the same way (each dx pixel depends on one dy pixel; dy is converted to
+    planes by the backward, the filter comes from the prepared transposed planes).  The assertions are that test's: inside the relative
+    window < 1e-6 of sum|ab| and < 2 x the exact-fp32 pipe's own error per pixel, the absolute floor outside."""
+    import torch.nn.functional as F
+    from pylc_amd import ops, layers, optim
+    from pylc_amd.lib import lib, check
+    b, cin, cout, hw = 1, 256, 128, 32
+    g = torch.Generator().manual_seed(7)
+    expo = torch.linspace(0, -14, hw * hw).reshape(1, 1, hw, hw)         # pixel magnitudes from 1 down to 1e-14
+    x = torch.randn(b, cin, hw, hw, generator=g) * 10.0 ** expo
+    wt = torch.randn(cout, cin, 1, 1, generator=g) * 0.05
+    dy = torch.randn(b, cout, hw, hw, generator=g) * 10.0 ** expo
+    x64 = x.double().requires_grad_(True)
+    ref_y = F.conv2d(x64, wt.double())
+    ref_dx, = torch.autograd.grad(ref_y, x64, dy.double())
+    ref = {'y': ref_y.detach(), 'dx': ref_dx}
+    scale = {'y': F.conv2d(x.double().abs(), wt.double().abs()), 'dx': F.conv_transpose2d(dy.double().abs(), wt.double().abs())}
+    conv = layers.Conv2d(cin, cout, 1).to(dev)
+    with torch.no_grad():
+        conv.weight.copy_(wt.to(dev))
+    arena = optim.FlatArena(conv)                                        # ranges and prepared filter planes of the weights just set
+    assert conv.weight._pylc_planes is not None and arena is not None
+    out = {}
+    conversions = ops.plane_conversions[0]
+    xp = ops.to_planes(nhwc(x, dev))
+    assert ops.is_planes(xp)
+    with torch.no_grad():
+        y = conv(xp)
+    xg = nhwc(x, dev).requires_grad_(True)
+    dx, = torch.autograd.grad(conv(xg), xg, nhwc(dy, dev))               # (training graph: x and dy both converted to planes on the way)
+    ops.sync_side_streams()
+    torch.cuda.synchronize()
+    assert ops.plane_conversions[0] == conversions, 'a planes operand was converted back to fp32: the fp32-operand kernels ran'
+    out[2] = {'y': y.double().cpu(), 'dx': dx.double().cpu()}
+    check(lib.pylc_set_conv_precision(0))                                # the exact-fp32 pipe on fp32 operands
+    try:
+        xg = nhwc(x, dev).requires_grad_(True)
+        y0 = conv(xg)
+        dx0, = torch.autograd.grad(y0, xg, nhwc(dy, dev))
+        ops.sync_side_streams()
+        torch.cuda.synchronize()
+        out[0] = {'y': y0.detach().double().cpu(), 'dx': dx0.double().cpu()}
+    finally:
+        check(lib.pylc_set_conv_precision(2))
+    mag = (10.0 ** expo).flatten()
+    inside = mag >= 2.0 ** -24          # elements ~N(0, mag) vs a tensor maximum of ~4.5: comfortably inside the relative window
+    amax = {'y': x.abs().max().item(), 'dx': dy.abs().max().item()}
+    wsum = {'y': wt.abs().sum(dim=1).max().item(), 'dx': wt.abs().sum(dim=0).max().item()}
+    for name in ('y', 'dx'):
+        rel = {m: ((out[m][name] - ref[name]).abs() / scale[name]).amax(dim=1).flatten() for m in out}       # per pixel, worst channel
+        print('planes %s: per-pixel error / sum|ab|, pixels within 2^24 of the largest: f32-mfma %.3g, f16x3 planes %.3g; at 1e-12 of the max: %.3g'
+              % (name, rel[0][inside].max(), rel[2][inside].max(), rel[2][(mag < 2e-12) & (mag > 5e-13)].max()))
+        assert rel[2][inside].max() < 1e-6, name
+        assert rel[2][inside].max() < 2.0 * rel[0][inside].max(), name
+        floor = 2.0 ** -50 * amax[name] * wsum[name]          # absolute error bound for the tiny pixels
+        assert ((out[2][name] - ref[name]).abs().amax(dim=1).flatten()[~inside] < floor + 1e-6 * scale[name].amax(dim=1).flatten()[~inside]).all(), name
