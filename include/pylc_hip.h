@@ -925,14 +925,24 @@ int pylc_multiloss_bwd_w(const float* logits, int pitch, const void* target, int
  * models/model.py:240-245 over ONE flat fp32 arena holding every parameter.
  * ------------------------------------------------------------------------------------------- */
 size_t pylc_sqnorm_workspace_floats(long long n);
-/* out[0] = ||g||_2, out[1] = clip coefficient min(1, max_norm / (||g|| + 1e-6)). */
+/* out[0] = ||g||_2, out[1] = clip coefficient min(1, max_norm / (||g|| + 1e-6)).
+ * Non-finite gradients follow torch.nn.utils.clip_grad_norm_ (error_if_nonfinite = False), nothing is tested or reported here:
+ *   a NaN anywhere in g:               out[0] = NaN, out[1] = NaN.  The update kernels read g * coef[1], so the step that follows turns
+ *                                      EVERY element of p (and of m, v / buf) into NaN, as the reference's does -- never a silent,
+ *                                      unclipped update of the finite elements;
+ *   an infinity (or a sum of squares   out[0] = +inf, out[1] = 0.  The step sees g * 0: zero for the finite elements, NaN at the
+ *   beyond fp32) and no NaN:           infinite ones.
+ * A caller that wants to skip such a step reads out[0].  workspace: pylc_sqnorm_workspace_floats(n) floats, contents undefined. */
 int pylc_grad_norm_clip(const float* g, long long n, float max_norm, float* out2, float* workspace, void* stream);
-/* p,m,v updated in place; g is read as g * coef[1] (coef = out2 of pylc_grad_norm_clip, or NULL for 1). */
+/* p,m,v updated in place; g is read as g * coef[1] (coef = out2 of pylc_grad_norm_clip, or NULL for 1).
+ * The decoupled decay multiplies p by the fp32 value 1.f - lr * weight_decay: for lr * weight_decay < 2^-25 (the reference's 1e-4 and
+ * 5e-5 give 5e-9) that factor is exactly 1 and the decay is the identity, as it is in torch.optim.AdamW's fp32 arithmetic. */
 int pylc_adamw_step(float* p, const float* g, float* m, float* v, long long n, const float* coef,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 /* pylc_adamw_step that also returns, per parameter segment [seg_offsets[s], seg_offsets[s+1]) of the arena (DEVICE int64[seg_count + 1],
  * multiples of 4, seg_offsets[0] = 0, seg_offsets[seg_count] = n), the IEEE bits of max|p| AFTER the update -- what pylc_amax_segments
- * would read back in a pass of its own (same values, bit for bit).  n % 4 == 0. */
+ * would read back in a pass of its own (same values, bit for bit).  n % 4 == 0.  The table has seg_count + 1 entries and the kernel
+ * READS the last one, seg_offsets[seg_count], as the end of the last segment; seg_amax_bits has seg_count entries, all rewritten. */
 int pylc_adamw_step_ranges(float* p, const float* g, float* m, float* v, long long n, const float* coef,
                            float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                            const long long* seg_offsets, int seg_count, unsigned int* seg_amax_bits, void* stream);

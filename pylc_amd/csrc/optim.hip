@@ -35,7 +35,9 @@ __global__ void norm_clip_finalize_kernel(const float* __restrict__ partial, int
         const float total = (float)sqrt(red[0]);
         float coef = max_norm / (total + 1e-6f);          // torch.nn.utils.clip_grad_norm_: clamp(max_norm/(total+1e-6), max=1)
         out2[0] = total;
-        out2[1] = coef < 1.f ? coef : 1.f;
+        // a NaN norm gives a NaN coefficient, as torch's clamp(max=1) does: the step then turns every parameter into NaN instead of
+        // updating the finite elements unclipped and leaving the loss to find out (`coef < 1 ? coef : 1` alone would give 1)
+        out2[1] = coef < 1.f ? coef : (coef != coef ? coef : 1.f);
     }
 }
 

@@ -178,6 +178,9 @@ class _FlatOptimizer:
         self.arena.begin_step()
 
     def _clip(self):
+        """Norm and clip coefficient into self.norm (None when clip is None: the kernels then read g unscaled).  Nothing here reads the
+        norm on the host: a NaN gradient gives a NaN coefficient and the step turns every parameter into NaN, as the reference's
+        clip_grad_norm_ + optimiser do (include/pylc_hip.h: pylc_grad_norm_clip)."""
         a = self.arena
         self._skipped = a.clear_undelivered()
         if self.clip is None:

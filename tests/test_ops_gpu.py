@@ -463,6 +463,11 @@ def test_image_pack(dev):
 
 
 def test_adamw_clip(dev):
+    """Three clipped AdamW steps at the reference's settings against torch.optim.AdamW in fp32.  What this test cannot see: its gradient at
+    step t is t * g0 and every step is clipped to norm 0.5, so the clipped gradient is the SAME vector at every step, m_hat = g and
+    v_hat = g^2 whatever beta1 / beta2 are -- a kernel with beta2 = 0.99, beta1 = 0.5 or no weight decay (at lr = 1e-4, wd = 5e-5 the
+    fp32 decay factor is exactly 1) passes it unchanged -- and only p is compared, never m or v.  The betas, the bias correction, eps, the
+    decay and the moments are pinned per element in tests/test_optim_abi_gpu.py."""
     import ctypes as C
     from pylc_amd.lib import lib, check, ptr, stream
     n = 100003
