@@ -307,6 +307,9 @@ int pylc_dwconv3x3_dgrad(const PylcDwDesc* d, const float* dy, const float* w, f
 /* accumulate != 0: dx += the data gradient (dx holds the part of the tensor's other consumers: the block input of xception.py:88-97
  * feeds both the first depthwise conv of `rep` and the skip path) */
 int pylc_dwconv3x3_dgrad_acc(const PylcDwDesc* d, const float* dy, const float* w_c9, float* dx, int accumulate, void* stream);
+/* The filter gradient sums per-block partial rows [rows][9][C] in the workspace; pylc_dwconv3x3_wgrad_workspace(d) holds the most a launch
+ * writes (1024 rows).  A smaller workspace is accepted when it holds the rows of THIS launch (the strip kernels' block count at stride 1 /
+ * dilation 1, the row slabs otherwise); one that does not: PYLC_ERR_WORKSPACE, nothing is launched, dw is not written. */
 size_t pylc_dwconv3x3_wgrad_workspace(const PylcDwDesc* d);
 int pylc_dwconv3x3_wgrad(const PylcDwDesc* d, const float* x, const float* dy, float* dw,
                          void* workspace, size_t workspace_bytes, void* stream);
@@ -316,7 +319,13 @@ int pylc_dwconv3x3_wgrad(const PylcDwDesc* d, const float* x, const float* dy, f
  * 9 * w_amax * input bound (+ acc_bound when accumulating into a dx that already holds another consumer's part, which is re-scaled in the
  * same pass) -- and written to *_bound_out.  pylc_dwconv3x3_dgrad_h with dx_bound_out == NULL writes (and accumulates into) an fp32 dx:
  * the gradient of a block input, which other consumers add to in fp32.  Dense stride-1 / dilation-1 shapes only
- * (pylc_dwconv3x3_half_ok); stats_partial as in pylc_dwconv3x3_fwd_stats (NULL: none), taken from the fp32 values before rounding. */
+ * (pylc_dwconv3x3_half_ok: dense, C % 4 == 0 and stride 1 / dilation 1 with W >= 2, or a shape of the tiled kernels -- C % 8 == 0 and stride
+ * 1 / dilation 1 (W == 1 included), stride 2 / dilation 1 with even H and W, or stride 1 / dilation 2, each with the tensor below 2^31
+ * bytes and while pylc_debug_dw_tiles has its kernel enabled.  The predicate is authoritative: ask it, do not restate it.  Any other
+ * descriptor: PYLC_ERR_ARG, nothing is written); stats_partial as in pylc_dwconv3x3_fwd_stats (NULL: none), taken from the ROUNDED halves, the tensor the BatchNorm
+ * behind the conv reads.  pylc_dwconv3x3_dgrad_h reads acc_bound only when accumulate != 0 (with accumulate == 0 it may be NULL or anything).
+ * pylc_dwconv3x3_wgrad_h de-scales with the one fp32 factor 1 / (s_x s_dy): exact while that product is a normal fp32 number, which
+ * holds for every pair of bounds within 2^-40 .. 2^20 (the window the tests cover). */
 int pylc_dwconv3x3_half_ok(const PylcDwDesc* d);
 /* rows of the stats_partial buffer pylc_dwconv3x3_fwd_h fills ([rows][2][C]; 0: shape not eligible) -- the half kernels tile the image
  * differently from the fp32 strip kernels, so this is not pylc_dwconv3x3_fwd_stats_rows */
@@ -325,7 +334,8 @@ int pylc_dwconv3x3_fwd_h(const PylcDwDesc* d, const void* x_h, const unsigned in
                          void* y_h, unsigned int* y_bound_out, float* stats_partial, void* stream);
 /* pylc_dwconv3x3_fwd_h for inference on one-plane tensors (xception.py:29-31 under Model.test, models/model.py:367-382): x was scaled with
  * x_bound but its TRUE maximum is x_true_amax (left by the producing pylc_conv2d_fwd_bnact_ex); y is scaled with, and *y_bound_out receives,
- * 9 max|w| x_true_amax -- the bound does not inherit the looseness of x's.  No statistics. */
+ * 9 max|w| x_true_amax -- the bound does not inherit the looseness of x's.  No statistics.  x_true_amax <= x_bound is the caller's to keep
+ * (it is not checked: a larger value only loosens y's bound again). */
 int pylc_dwconv3x3_fwd_h_eval(const PylcDwDesc* d, const void* x_h, const unsigned int* x_bound, const unsigned int* x_true_amax, const float* w,
                               const unsigned int* w_amax, void* y_h, unsigned int* y_bound_out, void* stream);
 int pylc_dwconv3x3_dgrad_h(const PylcDwDesc* d, const void* dy_h, const unsigned int* dy_bound, const float* w_c9, const unsigned int* w_amax,

@@ -893,13 +893,17 @@ extern "C" int pylc_dwconv3x3_wgrad(const PylcDwDesc* d, const float* x, const f
     if (int rc = check_dw(d)) return rc;
     PYLC_REQUIRE(x && dy && dw && workspace, "dwconv_wgrad: null pointer");
     const Slab g = make_slab((long long)d->B * d->OH * d->OW, d->C);
-    if ((size_t)g.nslab * 9 * d->C * sizeof(float) > workspace_bytes)
-        return fail(PYLC_ERR_WORKSPACE, "dwconv_wgrad workspace too small");
     hipStream_t st = as_stream(stream);
     int nslab = g.nslab;
+    DwStrip s{};
     if (dw_fast(d)) {
-        const DwStrip s = make_strips(d, g.cols, g.RL);
-        nslab = cdiv(s.n_strips, s.strips_per_block);          // <= kDefaultSlabs by construction
+        s = make_strips(d, g.cols, g.RL);
+        nslab = cdiv(s.n_strips, s.strips_per_block);          // <= kDefaultSlabs by construction; may exceed g.nslab
+    }
+    // the rows this launch writes, not make_slab's: the strip kernel's block count is its own
+    if ((size_t)nslab * 9 * d->C * sizeof(float) > workspace_bytes)
+        return fail(PYLC_ERR_WORKSPACE, "dwconv_wgrad workspace too small");
+    if (dw_fast(d)) {
         hipLaunchKernelGGL((dw_strip_kernel<2>), dim3(nslab), dim3(256), 0, st, x, dy, static_cast<float*>(workspace), geom(d), s, g.cols, g.RL,
                            g.CV, 0);
     } else {
@@ -913,7 +917,8 @@ extern "C" int pylc_dwconv3x3_wgrad(const PylcDwDesc* d, const float* x, const f
 
 // ---- one-plane fp16 operands (precision mode 3) ------------------------------------------------------------------------------------
 extern "C" int pylc_dwconv3x3_half_ok(const PylcDwDesc* d) {
-    return (check_dw(d) == PYLC_OK && (dw_fast(d) || dw_tileg_ok(d)) && d->x_pitch == d->C && d->y_pitch == d->C && d->C % 4 == 0) ? 1 : 0;
+    // W == 1 has no strip form (dw_fast) but is a shape of the tiled stride-1 kernel, as pylc_dwconv3x3_bn_ok has always said
+    return (check_dw(d) == PYLC_OK && (dw_fast(d) || dw_tile_ok(d) || dw_tileg_ok(d)) && d->x_pitch == d->C && d->y_pitch == d->C && d->C % 4 == 0) ? 1 : 0;
 }
 
 // launches of the generic tiled kernels (stride 2 / dilation 2), LDS opt-in on first use
@@ -949,7 +954,7 @@ extern "C" int pylc_dwconv3x3_fwd_h(const PylcDwDesc* d, const void* x_h, const 
                                     void* y_h, unsigned int* y_bound_out, float* stats_partial, void* stream) {
     if (int rc = check_dw(d)) return rc;
     PYLC_REQUIRE(x_h && x_bound && w && w_amax && y_h && y_bound_out && pylc_dwconv3x3_half_ok(d),
-                 "dwconv_fwd_h: null pointer, or not a dense stride-1 / dilation-1 shape (pylc_dwconv3x3_half_ok)");
+                 "dwconv_fwd_h: null pointer, or not a shape of the half kernels (pylc_dwconv3x3_half_ok)");
     const DwHalf hf{x_bound, nullptr, w_amax, nullptr, y_bound_out};
     return dw_fwd_h_impl(d, x_h, w, y_h, stats_partial, hf, stream);
 }
@@ -1010,7 +1015,7 @@ extern "C" int pylc_dwconv3x3_dgrad_h(const PylcDwDesc* d, const void* dy_h, con
     if (int rc = check_dw(d)) return rc;
     const bool out_f32 = dx_bound_out == nullptr;          // dx (and what it accumulates into) stays fp32: the block-input gradient
     PYLC_REQUIRE(dy_h && dy_bound && w && w_amax && dx_h && (out_f32 || !accumulate || acc_bound) && pylc_dwconv3x3_half_ok(d),
-                 "dwconv_dgrad_h: null pointer, or not a dense stride-1 / dilation-1 shape (pylc_dwconv3x3_half_ok)");
+                 "dwconv_dgrad_h: null pointer, or not a shape of the half kernels (pylc_dwconv3x3_half_ok)");
     PYLC_REQUIRE(out_f32 || !accumulate || acc_bound != dx_bound_out, "dwconv_dgrad_h: the new bound needs its own scalar (the old one is read by every block)");
     const DwHalf hf{dy_bound, nullptr, w_amax, acc_bound, dx_bound_out};
     if (dw_tile_ok(d)) {
@@ -1062,7 +1067,7 @@ extern "C" int pylc_dwconv3x3_wgrad_h(const PylcDwDesc* d, const void* x_h, cons
                                       float* dw, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_dw(d)) return rc;
     PYLC_REQUIRE(x_h && x_bound && dy_h && dy_bound && dw && workspace && pylc_dwconv3x3_half_ok(d),
-                 "dwconv_wgrad_h: null pointer, or not a dense stride-1 / dilation-1 shape (pylc_dwconv3x3_half_ok)");
+                 "dwconv_wgrad_h: null pointer, or not a shape of the half kernels (pylc_dwconv3x3_half_ok)");
     const DwHalf hf{x_bound, dy_bound, nullptr, nullptr, nullptr};
     return dw_wgrad_h_impl(d, x_h, dy_h, dw, workspace, workspace_bytes, hf, stream);
 }

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+from tests import _dw      # noqa: E402
 from tests.conftest import needs_experimental      # noqa: E402
 
 
@@ -455,6 +456,7 @@ def test_half_depthwise_kernels_against_fp64(dev, c, b, h, w, stride, dil, tiles
         check(lib.pylc_dwconv3x3_fwd_h(C.byref(d), ptr(x_h), ptr(xb_t), ptr(wt), ptr(wa_t), ptr(y_h), ptr(yb), ptr(sums), stream()))
         bound = yb.view(torch.float32).item()
         assert abs(bound - 9 * wa * xb) <= 1e-5 * bound and float(y_ref.abs().max()) <= bound
+        assert yb.item() == _dw.bound_bits(np.float32(wa), np.float32(xb))          # by bits: every consumer derives its scale from them (tests/_dw.py)
         y = y_h.double() / _half_scale(bound)
         assert (y - y_ref).abs().max().item() <= 2.0 ** -10 * bound            # one fp16 rounding at the tensor's scale (+ fp32 accumulation)
         st = sums.double().sum(0)
@@ -469,12 +471,14 @@ def test_half_depthwise_kernels_against_fp64(dev, c, b, h, w, stride, dil, tiles
         dxb = torch.zeros(1, dtype=torch.int32, device=dev)
         check(lib.pylc_dwconv3x3_dgrad_h(C.byref(d), ptr(dy_h), ptr(dyb_t), ptr(wt), ptr(wa_t), ptr(dx_h), ptr(dxb), 0, None, stream()))
         bd = dxb.view(torch.float32).item()
+        assert dxb.item() == _dw.bound_bits(np.float32(wa), np.float32(dyb))
         assert (dx_h.double() / _half_scale(bd) - dx_ref).abs().max().item() <= 2.0 ** -10 * bd
         acc_h = old_h.clone()
         dxb2 = torch.zeros(1, dtype=torch.int32, device=dev)
         check(lib.pylc_dwconv3x3_dgrad_h(C.byref(d), ptr(dy_h), ptr(dyb_t), ptr(wt), ptr(wa_t), ptr(acc_h), ptr(dxb2), 1, ptr(ob_t), stream()))
         bd2 = dxb2.view(torch.float32).item()
         assert abs(bd2 - (bd + ob)) <= 1e-5 * bd2
+        assert dxb2.item() == _dw.bound_bits(np.float32(wa), np.float32(dyb), np.float32(ob))
         assert (acc_h.double() / _half_scale(bd2) - (dx_ref + oldq)).abs().max().item() <= 2.0 ** -10 * bd2
         dx32 = old.clone()
         check(lib.pylc_dwconv3x3_dgrad_h(C.byref(d), ptr(dy_h), ptr(dyb_t), ptr(wt), ptr(wa_t), ptr(dx32), None, 1, None, stream()))
