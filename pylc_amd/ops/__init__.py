@@ -11,6 +11,10 @@ Layout of the package (one flat namespace: everything is re-exported here, `ops.
     bn.py      BnActFn, GroupBnActFn, bn_act, the SyncBN message driver
     dw.py      DwConv3x3Fn, dwconv3x3, the inference half form
     misc.py    ReLU, dropout, max-pool, concat, bilinear, global average pool, image pack, MultiLoss
+An operator that is also run without an autograd node (pylc_amd.torch_ops, the members of GroupBnActFn) is three things side by side: a
+plain `<op>_forward(needs_input_grad, arguments) -> (outputs, tensors to save, record, non-differentiable outputs)`, a plain
+`<op>_backward(record, saved tensors, needs_input_grad, gradient) -> gradients`, and a `__slots__` record (ConvState, BnState, ...) that
+states what the backward reads; its Function only adapts the pair to autograd and keeps the record as `ctx.st`.
 The few module-level SWITCHES that callers re-bind (`ops.PLANES_MIN_PIXELS = 0`, `ops.bn_timing = []`, `ops.mark_hook = fn`) live in
 _core and are forwarded by properties of this module, so that an assignment here reaches the code that reads them."""
 import sys

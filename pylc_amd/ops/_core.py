@@ -702,6 +702,18 @@ class ResidualLink:
     def armed(self):
         return self.pending > 0
 
+    def arm(self):
+        """Forward of a node that will add its part of x's gradient into the shared buffer: counts it; returns the link for its record."""
+        self.pending += 1
+        return self
+
+    def hand_over(self, dx):
+        """Backward of an armed node, once its part is in `dx`: returns what the node returns as x's gradient -- None while other consumers
+        of x follow (they accumulate into the same buffer), the buffer itself from the last one."""
+        self.pending -= 1
+        self.buf = dx if self.pending > 0 else None
+        return None if self.pending > 0 else dx
+
 
 def _link_sink(link):
     """The buffer a backward node accumulates its part of x's gradient into (None: nothing parked yet).  A parked (dout, mask) pair is
@@ -729,6 +741,51 @@ def grad_link(x):
         link = ResidualLink()
         x._pylc_link = link
     return link
+
+
+def concat_slice(into, b, c, h, w, what, ok=True):
+    """into = ([buffer], c0): channels [c0, c0 + c) of a caller-owned NHWC concat buffer (aspp.py:80, decoder.py:47) that a [b, c, h, w] result
+    is written into -> (the slice, the buffer's pitch).  `ok`: the caller's own extra conditions."""
+    buf, c0 = into[0][0], into[1]
+    if not ok or tuple(buf.shape[2:]) != (h, w) or buf.shape[0] != b or c0 % 4 or c0 + c > buf.shape[1]:
+        raise L.PylcError('%s into=: slice [%d, %d) does not fit the %s buffer' % (what, c0, c0 + c, tuple(buf.shape)))
+    return buf[:, c0:c0 + c], pitch_of(buf)
+
+
+def bias_grad(bias, dy, cout, dy_pl=False):
+    """The gradient of a conv bias, delivered: the per-channel column sums of dy (fp16 planes or fp32 rows, one read pass either way), copied
+    into the arena view of `bias` when the optimiser registered one, else a fresh tensor."""
+    m = dy.shape[0] * dy.shape[2] * dy.shape[3]
+    cp = _r4(cout)
+    sums = torch.empty(2 * cp, device=dy.device)
+    if dy_pl:
+        ws = torch.empty(lib.pylc_planes_colsum_workspace_floats(cout), device=dy.device)
+        check(lib.pylc_planes_colsum(ptr(dy), cout, pstride(m, cout), nplanes(), ptr(planes_amax(dy)), m, cout, ptr(sums), ptr(ws), stream()))
+    else:
+        ws = torch.empty(lib.pylc_bn_workspace_floats(m, cp), device=dy.device)
+        check(lib.pylc_bn_stats(ptr(dy), m, cp, pitch_of(dy), ptr(sums), ptr(ws), stream()))
+    tgt = _grad_target(bias)
+    if tgt is not None:
+        tgt.copy_(sums[:cout])
+        return _deliver_grad(bias, tgt)
+    return sums[:cout].clone()
+
+
+def _adapt(ctx, driven):
+    """The autograd half of every Function.forward whose kernels a plain driver function runs: `driven` is the driver's (outputs, tensors to
+    save, backward-state record, non-differentiable outputs)."""
+    outs, saved, ctx.st, nondiff = driven
+    ctx.save_for_backward(*saved)
+    if nondiff:
+        ctx.mark_non_differentiable(*nondiff)
+    return outs
+
+
+def _adapt_back(ctx, driver, dy):
+    """The autograd half of such a Function's backward: the driver's gradients of the leading arguments, None for the rest (and for all of
+    them when no gradient arrived)."""
+    grads = () if dy is None else driver(ctx.st, ctx.saved_tensors, ctx.needs_input_grad, dy)
+    return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
 
 
 __all__ = [n for n in dir() if not n.startswith('__')]      # everything, underscore helpers included: the package re-exports it (pylc_amd/ops/__init__.py)

@@ -3,6 +3,15 @@ fused inference conv + BatchNorm (fp32 and fp16-plane tensors).  Replaces nn.Con
 models/modules/aspp.py, models/decoder.py, models/architectures/unet.py."""
 from . import _core
 from ._core import *      # noqa: F401,F403  (layout / planes / range / stream helpers, lib bindings, torch)
+from .bn import bn_node_of
+
+
+def pad_stem_filter(w, cin):
+    """The thin-input stem filter ([Cout, 3, k, k]) zero-padded to the `cin`-channel input pack, KRSC (uncached)."""
+    cout, cin_w, r, s = w.shape
+    w_k = torch.zeros((cout, r, s, cin), device=w.device, dtype=torch.float32)
+    w_k[..., :cin_w] = w.detach().permute(0, 2, 3, 1)
+    return w_k
 
 
 def _padded_stem_filter(w, cin):
@@ -15,324 +24,312 @@ def _padded_stem_filter(w, cin):
     cache = getattr(w, '_pylc_w4', None)
     if cache is not None and cache[0] == key:
         return cache[1]
-    cout, cin_w, r, s = w.shape
-    w_k = torch.zeros((cout, r, s, cin), device=w.device, dtype=torch.float32)
-    w_k[..., :cin_w] = w.detach().permute(0, 2, 3, 1)
+    w_k = pad_stem_filter(w, cin)
     w._pylc_w4 = (key, w_k)
     return w_k
 
 
-class Conv2dFn(torch.autograd.Function):
-    """y = conv2d(x, w) + bias on the MFMA implicit-GEMM kernels."""
+class ConvState:
+    """What conv2d_backward reads besides the saved tensors (x, w_k).  The defaults are the plain functional case."""
+    __slots__ = ('geom', 'w_param', 'b_param', 'ranges', 'x_pl', 'dy_pl_ok', 'res_link', 'bn_src')
 
-    @staticmethod
-    def forward(ctx, x, w, bias, stride, pad, dil, want_stats=False, x_amax=None, w_amax=None, res_link=None, out=None, convert=False, bn_src=None):
-        L.init()
-        ctx.set_materialize_grads(False)      # the auxiliary outputs (statistics, ranges) carry no gradient: no zero fills
-        ctx.res_link = res_link if (res_link is not None and ctx.needs_input_grad[0]) else None
-        if ctx.res_link is not None:
-            res_link.pending += 1
-        ctx.bn_src = bn_src if ctx.needs_input_grad[0] else None      # the BatchNorm node that produced x (ops.conv2d): see backward
-        cout, cin_w, r, s = w.shape
-        b_, _, h_, w_ = x.shape
-        # (a bias is added by the planes kernels' epilogue like any other; its gradient is a column sum over the dy planes,
-        # pylc_planes_colsum)
-        takes = conv_takes_planes(w, b_ * h_ * w_, 0) and w_amax is not None and out is None
-        if takes and not is_planes(x) and convert:
-            # (convert: training graphs only -- grad mode as seen by ops.conv2d; inference keeps fp32 operands and the kernels the
-            # fused conv + BatchNorm epilogue path runs)
-            # one pass; the forward AND the wgrad then copy their operand tiles instead of splitting them.  A tensor read by several
-            # convs (projection blocks, the ASPP input) is converted once: the planes copy rides on the tensor object
-            cache = getattr(x, '_pylc_plcache', None)
-            if cache is not None and cache[1] == x._version:
-                x = cache[0]
-            else:
-                src = x
-                x = to_planes(x, x_amax)
-                src._pylc_plcache = (x, src._version)
-        x_pl = takes and is_planes(x)
-        if not x_pl:
-            x = as_nhwc(x)
-            if _runtime.debug_planes:
-                print('[pylc] conv fwd on fp32 operands: x %s w %s takes=%s grad=%s' % (tuple(x.shape), tuple(w.shape), takes, torch.is_grad_enabled()), flush=True)
-        cin = x.shape[1]
-        xp = pitch_of(x)
-        w_k = w
-        if cin_w % 4 != 0:
-            # thin-input stem (Cin=3): zero-pad the KRSC rows to 4 channels; x must already be the 4-channel pack
-            if cin != _r4(cin_w):
-                raise L.PylcError('conv expects the %d-channel packed input for a %d-channel filter' % (_r4(cin_w), cin_w))
-            w_k = _padded_stem_filter(w, cin)
-        elif cin != cin_w:
-            raise L.PylcError('conv: input has %d channels, filter expects %d' % (cin, cin_w))
-        elif not (w.permute(0, 2, 3, 1).is_contiguous()):
-            raise L.PylcError('conv weight must have KRSC (channels_last) memory')
-        b, _, h, wd = x.shape
-        oh, ow = conv_out_size(h, r, stride, pad, dil), conv_out_size(wd, s, stride, pad, dil)
-        if out is not None:
-            # write into channels [0, cout) of a caller-owned NHWC buffer (a concat target): out = [buffer]
-            buf = out[0]
-            yp = pitch_of(buf)
-            if tuple(buf.shape[2:]) != (oh, ow) or buf.shape[0] != b or buf.shape[1] < cout or cout % 4:
-                raise L.PylcError('conv out= buffer %s does not fit a [%d,%d,%d,%d] result' % (tuple(buf.shape), b, cout, oh, ow))
-            y = buf[:, :cout]
+    def __init__(self, geom, w_param, b_param, ranges=(None, None), x_pl=False, dy_pl_ok=False, res_link=None, bn_src=None):
+        self.geom, self.w_param, self.b_param, self.ranges = geom, w_param, b_param, ranges      # geom: (stride, pad, dil, filter Cin, has bias)
+        self.x_pl, self.dy_pl_ok = x_pl, dy_pl_ok      # x was saved as fp16 planes; dy may come back as planes (BatchNorm backward writes them)
+        self.res_link, self.bn_src = res_link, bn_src      # the armed gradient link of x; the BatchNorm node that produced x (ops.conv2d)
+
+
+def conv2d_forward(needs, x, w, bias, stride, pad, dil, want_stats=False, x_amax=None, w_amax=None, res_link=None, out=None, convert=False,
+                   bn_src=None):
+    """Drives Conv2dFn's forward kernels.  needs: needs_input_grad of (x, w, bias).  Returns (y | (y, sums) | (y, sums, y_bound), tensors to
+    save, ConvState, non-differentiable outputs)."""
+    L.init()
+    res_link = res_link.arm() if (res_link is not None and needs[0]) else None
+    bn_src = bn_src if needs[0] else None
+    cout, cin_w, r, s = w.shape
+    b_, _, h_, w_ = x.shape
+    # (a bias is added by the planes kernels' epilogue like any other; its gradient is a column sum over the dy planes,
+    # pylc_planes_colsum)
+    takes = conv_takes_planes(w, b_ * h_ * w_, 0) and w_amax is not None and out is None
+    if takes and not is_planes(x) and convert:
+        # (convert: training graphs only -- grad mode as seen by ops.conv2d; inference keeps fp32 operands and the kernels the
+        # fused conv + BatchNorm epilogue path runs)
+        # one pass; the forward AND the wgrad then copy their operand tiles instead of splitting them.  A tensor read by several
+        # convs (projection blocks, the ASPP input) is converted once: the planes copy rides on the tensor object
+        cache = getattr(x, '_pylc_plcache', None)
+        if cache is not None and cache[1] == x._version:
+            x = cache[0]
         else:
-            yp = _r4(cout)
-            y = empty_nhwc(b, cout, oh, ow, x.device, yp)
-        d = _conv_desc(x, cin, cout, r, s, stride, pad, dil, xp, yp)
-        if x_pl:
-            d.x_fmt = 1
-            x_amax = planes_amax(x)          # the bound the producer scaled the planes with
-        d.x_amax, d.w_amax = ptr(x_amax), ptr(w_amax)
-        ctx.ranges = (x_amax, w_amax)
-        ctx.x_pl = x_pl
-        # precision mode 3: y leaves as one fp16 plane when a BatchNorm is going to read it (want_stats) -- half the bytes of the store-bound
-        # epilogue and of the three BatchNorm passes over y
-        y_bound = None
-        if want_stats and x_pl and convert and half_acts() and bias is None and out is None and cout % 8 == 0 and yp == cout and planes_ok(cout, b * oh * ow):
-            y_bound = amax_slot(x.device)
-            d.out_fmt, d.out_bound = 1, ptr(y_bound)
-        planes = getattr(w, '_pylc_planes', None) if (w_amax is not None and w_k is w) else None
+            src = x
+            x = to_planes(x, x_amax)
+            src._pylc_plcache = (x, src._version)
+    x_pl = takes and is_planes(x)
+    if not x_pl:
+        x = as_nhwc(x)
+        if _runtime.debug_planes:
+            print('[pylc] conv fwd on fp32 operands: x %s w %s takes=%s grad=%s' % (tuple(x.shape), tuple(w.shape), takes, torch.is_grad_enabled()), flush=True)
+    cin = x.shape[1]
+    xp = pitch_of(x)
+    w_k = w
+    if cin_w % 4 != 0:
+        # thin-input stem (Cin=3): zero-pad the KRSC rows to 4 channels; x must already be the 4-channel pack
+        if cin != _r4(cin_w):
+            raise L.PylcError('conv expects the %d-channel packed input for a %d-channel filter' % (_r4(cin_w), cin_w))
+        w_k = _padded_stem_filter(w, cin)
+    elif cin != cin_w:
+        raise L.PylcError('conv: input has %d channels, filter expects %d' % (cin, cin_w))
+    elif not (w.permute(0, 2, 3, 1).is_contiguous()):
+        raise L.PylcError('conv weight must have KRSC (channels_last) memory')
+    b, _, h, wd = x.shape
+    oh, ow = conv_out_size(h, r, stride, pad, dil), conv_out_size(wd, s, stride, pad, dil)
+    if out is not None:
+        # write into channels [0, cout) of a caller-owned NHWC buffer (a concat target): out = [buffer]
+        buf = out[0]
+        yp = pitch_of(buf)
+        if tuple(buf.shape[2:]) != (oh, ow) or buf.shape[0] != b or buf.shape[1] < cout or cout % 4:
+            raise L.PylcError('conv out= buffer %s does not fit a [%d,%d,%d,%d] result' % (tuple(buf.shape), b, cout, oh, ow))
+        y = buf[:, :cout]
+    else:
+        yp = _r4(cout)
+        y = empty_nhwc(b, cout, oh, ow, x.device, yp)
+    d = _conv_desc(x, cin, cout, r, s, stride, pad, dil, xp, yp)
+    if x_pl:
+        d.x_fmt = 1
+        x_amax = planes_amax(x)          # the bound the producer scaled the planes with
+    d.x_amax, d.w_amax = ptr(x_amax), ptr(w_amax)
+    # precision mode 3: y leaves as one fp16 plane when a BatchNorm is going to read it (want_stats) -- half the bytes of the store-bound
+    # epilogue and of the three BatchNorm passes over y
+    y_bound = None
+    if want_stats and x_pl and convert and half_acts() and bias is None and out is None and cout % 8 == 0 and yp == cout and planes_ok(cout, b * oh * ow):
+        y_bound = amax_slot(x.device)
+        d.out_fmt, d.out_bound = 1, ptr(y_bound)
+    planes = getattr(w, '_pylc_planes', None) if (w_amax is not None and w_k is w) else None
+    if planes is not None:
+        d.w_planes, d.w_planes_fmt = ptr(planes[0]), filter_planes_fmt(planes)
+    ev = None
+    if _core._timer is not None and (x_pl if _core._timer.planes else _is_dominant_tile(b * oh * ow, yp, cin, r * s)):
+        ev = _core._timer.bracket(2.0 * b * oh * ow * cout * r * s * cin, 1, 'fwd%dx%d' % (r, s),
+                            4.0 * (b * h * wd * cin + cout * r * s * cin + b * oh * ow * cout))
+        ev[0].record()
+    sums = None
+    if want_stats:
+        if cout % 4:
+            raise L.PylcError('fused BatchNorm statistics need Cout % 4 == 0')
+        part = torch.empty(lib.pylc_conv2d_fwd_stats_floats(C.byref(d)), device=x.device)
+        rows = C.c_int(0)
+        check(lib.pylc_conv2d_fwd_stats(C.byref(d), ptr(x), ptr(w_k), ptr(bias), ptr(y), ptr(part), C.byref(rows), stream()))
+        sums = part[:rows.value * 2 * cout].view(rows.value, 2 * cout)      # per-tile partials; the BatchNorm combines them
+    else:
+        check(lib.pylc_conv2d_fwd(C.byref(d), ptr(x), ptr(w_k), ptr(bias), ptr(y), stream()))
+    if ev is not None:
+        ev[1].record()
+    # dy may come back as fp16 planes (BatchNorm backward writes them) when the backward kernels can take them
+    st = ConvState((stride, pad, dil, cin_w, bias is not None), w, bias, (x_amax, w_amax), x_pl,
+                   x_pl and cout % 8 == 0 and ow >= 16 and planes_ok(cout, b * oh * ow) and yp == cout, res_link, bn_src)
+    aux = tuple(t for t in (sums, y_bound) if t is not None)
+    return ((y,) + aux if aux else y), (x, w_k), st, aux
+
+
+def conv2d_backward(state, saved, needs, dy):
+    """Drives Conv2dFn's backward kernels: (ConvState, (x, w_k), needs_input_grad of (x, w, bias), dy) -> (dx, dw, db)."""
+    x, w_k = saved
+    flush_deferred_wgrad(x.device)
+    stride, pad, dil, cin_w, has_bias = state.geom
+    w, bias = state.w_param, state.b_param
+    x_pl = state.x_pl
+    if x_pl:
+        mark_planes(x, state.ranges[0])       # saved tensors come back as new Python objects: restore the marker
+    dy_pl = is_planes(dy)
+    if x_pl and _runtime.planes_fwd_only:          # debug: planes in the forward pass only
+        x, x_pl = from_planes(x), False
+    if dy_pl and not x_pl:
+        dy, dy_pl = from_planes(dy), False
+    elif x_pl and not dy_pl:
+        dy = as_nhwc(dy)
+        if dy.shape[1] % 8 == 0 and pitch_of(dy) == dy.shape[1] and planes_ok(dy.shape[1], dy.shape[0] * dy.shape[2] * dy.shape[3]) \
+                and dy.shape[3] >= 16:
+            dy, dy_pl = to_planes(dy), True           # one pass; dgrad and wgrad then both read planes
+        else:
+            x, x_pl = from_planes(x), False
+    if not dy_pl:
+        dy = as_nhwc(dy)
+        if _runtime.debug_planes:
+            print('[pylc] conv bwd on fp32 operands: x %s w %s x_pl=%s dy_pl_ok=%s' % (tuple(x.shape), tuple(w.shape), state.x_pl, state.dy_pl_ok), flush=True)
+    cout, _, r, s = w.shape
+    cin = x.shape[1]
+    yp = pitch_of(dy)
+    if yp < _r4(cout):      # a grad produced outside our kernels: re-pitch so vector loads stay in bounds
+        t = zeros_nhwc(dy.shape[0], cout, dy.shape[2], dy.shape[3], dy.device, _r4(cout))
+        t.copy_(dy)
+        dy, yp = t, _r4(cout)
+    d = _conv_desc(x, cin, cout, r, s, stride, pad, dil, pitch_of(x), yp)
+    d.x_fmt, d.dy_fmt = int(x_pl), int(dy_pl)
+    x_amax, w_amax = state.ranges
+    dy_amax = None
+    if ranges_needed():
+        if x_amax is None or w_amax is None:
+            raise L.PylcError('conv backward in f16x3 mode, but the forward ran without operand ranges')
+        dy_amax = planes_amax(dy) if dy_pl else amax_of(dy)
+        d.x_amax, d.w_amax, d.dy_amax = ptr(x_amax), ptr(w_amax), ptr(dy_amax)
+        planes = getattr(w, '_pylc_planes', None) if w_k is w else None
         if planes is not None:
-            d.w_planes, d.w_planes_fmt = ptr(planes[0]), filter_planes_fmt(planes)
-        ev = None
-        if _core._timer is not None and (x_pl if _core._timer.planes else _is_dominant_tile(b * oh * ow, yp, cin, r * s)):
-            ev = _core._timer.bracket(2.0 * b * oh * ow * cout * r * s * cin, 1, 'fwd%dx%d' % (r, s),
-                                4.0 * (b * h * wd * cin + cout * r * s * cin + b * oh * ow * cout))
-            ev[0].record()
-        sums = None
-        if want_stats:
-            if cout % 4:
-                raise L.PylcError('fused BatchNorm statistics need Cout % 4 == 0')
-            part = torch.empty(lib.pylc_conv2d_fwd_stats_floats(C.byref(d)), device=x.device)
-            rows = C.c_int(0)
-            check(lib.pylc_conv2d_fwd_stats(C.byref(d), ptr(x), ptr(w_k), ptr(bias), ptr(y), ptr(part), C.byref(rows), stream()))
-            sums = part[:rows.value * 2 * cout].view(rows.value, 2 * cout)      # per-tile partials; the BatchNorm combines them
+            d.w_planes_t, d.w_planes_fmt = ptr(planes[1]), filter_planes_fmt(planes)
+    st = stream()
+    dx = dw = db = None
+    if needs[0]:
+        kp = _r4(cout)
+        link = state.res_link
+        masked = None
+        if (link is not None and link.masked is not None and link.buf is None and dy_pl and stride == 1 and cin % 8 == 0
+                and tuple(link.masked[0].shape) == tuple(x.shape)):
+            masked, link.masked = link.masked, None       # relu'(dout) is formed in this dgrad's epilogue: no buffer to accumulate into
+        sink = _link_sink(link)
+        if sink is not None:            # part of x's gradient is already in `sink`: dgrad adds to it (no autograd add pass)
+            dx = sink
         else:
-            check(lib.pylc_conv2d_fwd(C.byref(d), ptr(x), ptr(w_k), ptr(bias), ptr(y), stream()))
+            dx = empty_nhwc(*x.shape, device=x.device)
+        d.x_pitch = cin
+        # precision mode 3: dx leaves as one fp16 plane when it is the whole gradient of a BatchNorm output with this conv as its only
+        # consumer (nothing will be added to it: autograd would add the raw bytes)
+        dx_bound = None
+        bn = state.bn_src.st if state.bn_src is not None else None      # the record of the BatchNorm node that produced x
+        if (half_acts() and dy_pl and stride == 1 and sink is None and masked is None and link is None and cin % 8 == 0 and bn is not None
+                and bn.sole and not _runtime.fuse_bn_sums and planes_ok(cin, x.shape[0] * x.shape[2] * x.shape[3])):
+            dx_bound = amax_slot(x.device)
+            d.out_fmt, d.out_bound = 1, ptr(dx_bound)
+        wt = None
+        if lib.pylc_conv2d_dgrad_needs_f32_weights(C.byref(d)):      # else the prepared planes are all the kernel reads
+            wt = torch.empty((cin, r * s, kp), device=x.device, dtype=torch.float32)
+            check(lib.pylc_weight_transpose(ptr(w_k), ptr(wt), cout, r * s, cin, st))
+        ev = None
+        n_launch = 1 if stride == 1 else min(r, 2) * min(s, 2)     # one launch per non-empty output parity class
+        if _core._timer is not None and (dy_pl if _core._timer.planes else _is_dominant_tile(x.shape[0] * x.shape[2] * x.shape[3] // n_launch, cin, kp, 2)):
+            ev = _core._timer.bracket(2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * cout * r * s * cin, n_launch, 'dgrad%dx%d' % (r, s),
+                                4.0 * (dy.numel() + cout * r * s * cin + x.numel()))
+            ev[0].record()
+        # x is a BatchNorm's output and this dgrad writes its COMPLETE gradient (sole consumer, or the last consumer of the gradient
+        # link): the sums that BatchNorm's backward starts with are taken in this epilogue (pylc_conv2d_dgrad_bn) and handed to its
+        # node, which then skips its read pass over (dout, y)
+        emit = (bn is not None and dy_pl and stride == 1 and cin % 8 == 0 and _runtime.fuse_bn_sums and bn.pre_sums is None
+                and bn.bn_emit_ok and tuple(bn.y_shape) == tuple(x.shape)
+                and ((link is None and bn.sole) or (link is not None and link.pending == 1)))
+        if emit:
+            L._need_experimental('PYLC_RUNTIME=fuse_bn_sums=1')
+            y_bn, _, coef, _, bmask, _ = state.bn_src.saved_tensors
+            cb = x.shape[1]
+            relu_bn = bn.cfg[0]
+            bb = L.BnBack()
+            bb.y, bb.mean, bb.invstd = ptr(y_bn), ptr(coef[:cb]), ptr(coef[cb:2 * cb])
+            if relu_bn and bmask is None:
+                bb.scale, bb.shift = ptr(coef[2 * cb:3 * cb]), ptr(coef[3 * cb:])
+            bb.relu_mask, bb.relu = ptr(bmask) if relu_bn else None, int(relu_bn)
+            gmx = amax_slot(x.device)
+            bb.g_amax = ptr(gmx)
+            part = torch.empty(lib.pylc_conv2d_dgrad_bn_floats(C.byref(d)), device=x.device)
+            rows = C.c_int(0)
+            check(lib.pylc_conv2d_dgrad_bn(C.byref(d), ptr(dy), ptr(wt), ptr(dx), 1 if (sink is not None and masked is None) else 0,
+                                           ptr(masked[0]) if masked is not None else None, ptr(masked[1]) if masked is not None else None,
+                                           C.byref(bb), ptr(part), C.byref(rows), st))
+            bn.pre_sums = (part, rows.value, gmx)
+        elif masked is not None:
+            check(lib.pylc_conv2d_dgrad_add(C.byref(d), ptr(dy), ptr(wt), ptr(dx), 0, ptr(masked[0]), ptr(masked[1]), st))
+        else:
+            check(lib.pylc_conv2d_dgrad(C.byref(d), ptr(dy), ptr(wt), ptr(dx), 1 if sink is not None else 0, st))
         if ev is not None:
             ev[1].record()
-        ctx.save_for_backward(x, w_k)
-        # dy may come back as fp16 planes (BatchNorm backward writes them) when the backward kernels can take them
-        ctx.dy_pl_ok = x_pl and cout % 8 == 0 and ow >= 16 and planes_ok(cout, b * oh * ow) and yp == cout
-        ctx.geom = (stride, pad, dil, cin_w, bias is not None)
-        ctx.w_param, ctx.b_param = w, bias
-        if want_stats:
-            if y_bound is not None:
-                ctx.mark_non_differentiable(sums, y_bound)
-                return y, sums, y_bound
-            ctx.mark_non_differentiable(sums)
-            return y, sums
-        return y
+        d.x_pitch = pitch_of(x)
+        d.out_fmt, d.out_bound = 0, None
+        if dx_bound is not None:
+            mark_planes(dx, dx_bound)
+        if link is not None:
+            dx = link.hand_over(dx)
+    if needs[1]:
+        # wgrad is off the critical chain (only the optimiser needs it), so it runs on a side stream: the matrix-bound
+        # wgrad kernels then overlap the HBM-bound BatchNorm-backward kernels of the layers that follow on the main stream
+        side = _side_stream(x.device) if _runtime.side_stream_on() else None
+        tgt = _grad_target(w)
+
+        def launch_wgrad(side=side, tgt=tgt, x=x, dy=dy, w=w, w_k=w_k, d=d, dy_amax=dy_amax, x_amax=x_amax):   # bound now: it may run later
+            if side is not None:
+                ev = torch.cuda.Event()      # recorded AFTER the dgrad launch: wgrad starts when the dgrad is done (letting it
+                ev.record()                  # start next to the dgrad was measured 5 % slower, making every dgrad wait for the
+                                             # previous wgrad 2 % slower)
+                side.wait_event(ev)
+                _keep_for_side(x.device, x, dy, w_k, dy_amax, x_amax)
+            with torch.cuda.stream(side) if side is not None else _nullcontext():
+                sst = stream()
+                nbytes = lib.pylc_conv2d_wgrad_workspace(C.byref(d))
+                ws = _ws(nbytes, x.device)
+                if cin_w % 4 == 0 and tgt is not None and side is None and _runtime.batch_slab_sums and nbytes > 0:
+                    # one queue: the split-K slabs stay in this weight's OWN workspace and every layer's slab sum runs in one launch
+                    # before the gradients are read (ops.flush_slab_sums, from sync_side_streams / the gradient bucketer)
+                    own = getattr(w, '_pylc_slab_ws', None)
+                    if own is not None and own.is_cuda and _core.slab_sum_pending(own.device, own):
+                        # the same weight again in this pass: sum its first slabs before they are overwritten -- or, when the second plan
+                        # needs a larger block, before the old block goes back to the allocator with a noted sum still pointing at it
+                        _core.flush_slab_sums(own.device)
+                    if own is None or own.numel() * 4 < nbytes or own.device != x.device:
+                        own = w._pylc_slab_ws = torch.empty(nbytes // 4 + 1, device=x.device)
+                    dwl = tgt
+                    pend = L.SlabSum()
+                    check(lib.pylc_conv2d_wgrad_slabs(C.byref(d), ptr(x), ptr(dy), ptr(dwl), ptr(own), nbytes, C.byref(pend), sst))
+                    if pend.splits > 0:
+                        _core.add_slab_sum(x.device, pend)
+                elif cin_w % 4 == 0:
+                    dwl = tgt if tgt is not None else torch.empty((cout, r, s, cin), device=x.device).permute(0, 3, 1, 2)
+                    check(lib.pylc_conv2d_wgrad(C.byref(d), ptr(x), ptr(dy), ptr(dwl), None, ptr(ws), nbytes, sst))
+                else:
+                    dw4 = torch.empty((cout, r, s, cin), device=x.device)
+                    check(lib.pylc_conv2d_wgrad(C.byref(d), ptr(x), ptr(dy), ptr(dw4), None, ptr(ws), nbytes, sst))
+                    dwl = tgt if tgt is not None else torch.empty((cout, r, s, cin_w), device=x.device).permute(0, 3, 1, 2)
+                    dwl.copy_(dw4[..., :cin_w].permute(0, 3, 1, 2))
+            if side is not None and tgt is None:
+                torch.cuda.current_stream().wait_stream(side)      # the returned tensor is consumed by autograd on the main stream
+            return _deliver_grad(w, dwl)
+
+        hold = getattr(w, '_pylc_wgrad_hold', 0) if _runtime.wgrad_hold else 0
+        if hold and side is not None and tgt is not None:
+            # a layer-specific launch ORDER (set by the network, e.g. nets/deeplabv3p.py Decoder): this conv's wgrad fills every CU for
+            # milliseconds; started now it would sit in front of the short kernels that follow on the main queue (the 256->48 dgrad of
+            # decoder.py:27 waited 2 ms behind the 304->256 wgrad).  Held until `hold` further conv backwards have begun.
+            _defer_wgrad(x.device, launch_wgrad, hold)
+            dw = None
+        elif _runtime.defer_wgrad_1x1 and r * s == 1 and side is not None and tgt is not None:
+            # an HBM-heavy 1x1 wgrad started now would run beside the (HBM-bound) BatchNorm backward that follows on the main
+            # stream; held back until the NEXT conv backward begins, it runs beside that conv's matrix-bound dgrad instead
+            _defer_wgrad(x.device, launch_wgrad)
+            dw = None
+        else:
+            dw = launch_wgrad()
+    if has_bias and needs[2] and getattr(dy, '_pylc_zero_colsum', False) and _runtime.skip_zero_bias_grad:
+        # dy was written by the backward of a TRAINING-mode BatchNorm that reads this conv's output directly (unet.py:112-118):
+        # dy = k (g - mean g - xhat mean(g xhat)) sums to ZERO over the rows of every channel (sum xhat = 0), i.e. the loss does not
+        # depend on a bias that the batch mean removes again.  What a column sum over dy -- or autograd in the reference -- returns
+        # here is the rounding noise of that cancellation (tests/golden: these keys are the fixtures' `zero_grad_keys`), so the pass
+        # over dy is skipped and the gradient is the exact value.  (SyncBN: the sum over ALL ranks' rows is zero, and the gradient
+        # all-reduce adds the ranks' bias gradients.)
+        tgt = _grad_target(bias)
+        if tgt is not None:
+            tgt.zero_()
+            db = _deliver_grad(bias, tgt)
+        else:
+            db = torch.zeros_like(bias)
+    elif has_bias and needs[2]:
+        db = bias_grad(bias, dy, cout, dy_pl)
+    return dx, dw, db
+
+
+class Conv2dFn(torch.autograd.Function):
+    """y = conv2d(x, w) + bias on the MFMA implicit-GEMM kernels (conv2d_forward / conv2d_backward)."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.set_materialize_grads(False)      # the auxiliary outputs (statistics, ranges) carry no gradient: no zero fills
+        return _adapt(ctx, conv2d_forward(ctx.needs_input_grad, *args))
 
     @staticmethod
     def backward(ctx, dy, *_unused):
-        if dy is None:
-            return (None,) * 13
-        x, w_k = ctx.saved_tensors
-        flush_deferred_wgrad(x.device)
-        stride, pad, dil, cin_w, has_bias = ctx.geom
-        w, bias = ctx.w_param, ctx.b_param
-        x_pl = ctx.x_pl
-        if x_pl:
-            mark_planes(x, ctx.ranges[0])       # saved tensors come back as new Python objects: restore the marker
-        dy_pl = is_planes(dy)
-        if x_pl and _runtime.planes_fwd_only:          # debug: planes in the forward pass only
-            x, x_pl = from_planes(x), False
-        if dy_pl and not x_pl:
-            dy, dy_pl = from_planes(dy), False
-        elif x_pl and not dy_pl:
-            dy = as_nhwc(dy)
-            if dy.shape[1] % 8 == 0 and pitch_of(dy) == dy.shape[1] and planes_ok(dy.shape[1], dy.shape[0] * dy.shape[2] * dy.shape[3]) \
-                    and dy.shape[3] >= 16:
-                dy, dy_pl = to_planes(dy), True           # one pass; dgrad and wgrad then both read planes
-            else:
-                x, x_pl = from_planes(x), False
-        if not dy_pl:
-            dy = as_nhwc(dy)
-            if _runtime.debug_planes:
-                print('[pylc] conv bwd on fp32 operands: x %s w %s x_pl=%s dy_pl_ok=%s' % (tuple(x.shape), tuple(w.shape), ctx.x_pl, ctx.dy_pl_ok), flush=True)
-        cout, _, r, s = w.shape
-        cin = x.shape[1]
-        yp = pitch_of(dy)
-        if yp < _r4(cout):      # a grad produced outside our kernels: re-pitch so vector loads stay in bounds
-            t = zeros_nhwc(dy.shape[0], cout, dy.shape[2], dy.shape[3], dy.device, _r4(cout))
-            t.copy_(dy)
-            dy, yp = t, _r4(cout)
-        d = _conv_desc(x, cin, cout, r, s, stride, pad, dil, pitch_of(x), yp)
-        d.x_fmt, d.dy_fmt = int(x_pl), int(dy_pl)
-        x_amax, w_amax = ctx.ranges
-        dy_amax = None
-        if ranges_needed():
-            if x_amax is None or w_amax is None:
-                raise L.PylcError('conv backward in f16x3 mode, but the forward ran without operand ranges')
-            dy_amax = planes_amax(dy) if dy_pl else amax_of(dy)
-            d.x_amax, d.w_amax, d.dy_amax = ptr(x_amax), ptr(w_amax), ptr(dy_amax)
-            planes = getattr(w, '_pylc_planes', None) if w_k is w else None
-            if planes is not None:
-                d.w_planes_t, d.w_planes_fmt = ptr(planes[1]), filter_planes_fmt(planes)
-        st = stream()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            kp = _r4(cout)
-            link = ctx.res_link
-            masked = None
-            if (link is not None and link.masked is not None and link.buf is None and dy_pl and stride == 1 and cin % 8 == 0
-                    and tuple(link.masked[0].shape) == tuple(x.shape)):
-                masked, link.masked = link.masked, None       # relu'(dout) is formed in this dgrad's epilogue: no buffer to accumulate into
-            sink = _link_sink(link)
-            if sink is not None:            # part of x's gradient is already in `sink`: dgrad adds to it (no autograd add pass)
-                dx = sink
-            else:
-                dx = empty_nhwc(*x.shape, device=x.device)
-            d.x_pitch = cin
-            # precision mode 3: dx leaves as one fp16 plane when it is the whole gradient of a BatchNorm output with this conv as its only
-            # consumer (nothing will be added to it: autograd would add the raw bytes)
-            dx_bound = None
-            bn_node = ctx.bn_src
-            if (half_acts() and dy_pl and stride == 1 and sink is None and masked is None and link is None and cin % 8 == 0 and bn_node is not None
-                    and getattr(bn_node, 'sole', False) and not _runtime.fuse_bn_sums and planes_ok(cin, x.shape[0] * x.shape[2] * x.shape[3])):
-                dx_bound = amax_slot(x.device)
-                d.out_fmt, d.out_bound = 1, ptr(dx_bound)
-            wt = None
-            if lib.pylc_conv2d_dgrad_needs_f32_weights(C.byref(d)):      # else the prepared planes are all the kernel reads
-                wt = torch.empty((cin, r * s, kp), device=x.device, dtype=torch.float32)
-                check(lib.pylc_weight_transpose(ptr(w_k), ptr(wt), cout, r * s, cin, st))
-            ev = None
-            n_launch = 1 if stride == 1 else min(r, 2) * min(s, 2)     # one launch per non-empty output parity class
-            if _core._timer is not None and (dy_pl if _core._timer.planes else _is_dominant_tile(x.shape[0] * x.shape[2] * x.shape[3] // n_launch, cin, kp, 2)):
-                ev = _core._timer.bracket(2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * cout * r * s * cin, n_launch, 'dgrad%dx%d' % (r, s),
-                                    4.0 * (dy.numel() + cout * r * s * cin + x.numel()))
-                ev[0].record()
-            # x is a BatchNorm's output and this dgrad writes its COMPLETE gradient (sole consumer, or the last consumer of the gradient
-            # link): the sums that BatchNorm's backward starts with are taken in this epilogue (pylc_conv2d_dgrad_bn) and handed to its
-            # node, which then skips its read pass over (dout, y)
-            bn = ctx.bn_src
-            emit = (bn is not None and dy_pl and stride == 1 and cin % 8 == 0 and _runtime.fuse_bn_sums and getattr(bn, 'pre_sums', None) is None
-                    and getattr(bn, 'bn_emit_ok', False) and tuple(bn.y_shape) == tuple(x.shape)
-                    and ((link is None and bn.sole) or (link is not None and link.pending == 1)))
-            if emit:
-                L._need_experimental('PYLC_RUNTIME=fuse_bn_sums=1')
-                y_bn, _, coef, _, bmask, _ = bn.saved_tensors
-                cb = x.shape[1]
-                relu_bn = bn.cfg[0]
-                bb = L.BnBack()
-                bb.y, bb.mean, bb.invstd = ptr(y_bn), ptr(coef[:cb]), ptr(coef[cb:2 * cb])
-                if relu_bn and bmask is None:
-                    bb.scale, bb.shift = ptr(coef[2 * cb:3 * cb]), ptr(coef[3 * cb:])
-                bb.relu_mask, bb.relu = ptr(bmask) if relu_bn else None, int(relu_bn)
-                gmx = amax_slot(x.device)
-                bb.g_amax = ptr(gmx)
-                part = torch.empty(lib.pylc_conv2d_dgrad_bn_floats(C.byref(d)), device=x.device)
-                rows = C.c_int(0)
-                check(lib.pylc_conv2d_dgrad_bn(C.byref(d), ptr(dy), ptr(wt), ptr(dx), 1 if (sink is not None and masked is None) else 0,
-                                               ptr(masked[0]) if masked is not None else None, ptr(masked[1]) if masked is not None else None,
-                                               C.byref(bb), ptr(part), C.byref(rows), st))
-                bn.pre_sums = (part, rows.value, gmx)
-            elif masked is not None:
-                check(lib.pylc_conv2d_dgrad_add(C.byref(d), ptr(dy), ptr(wt), ptr(dx), 0, ptr(masked[0]), ptr(masked[1]), st))
-            else:
-                check(lib.pylc_conv2d_dgrad(C.byref(d), ptr(dy), ptr(wt), ptr(dx), 1 if sink is not None else 0, st))
-            if ev is not None:
-                ev[1].record()
-            d.x_pitch = pitch_of(x)
-            d.out_fmt, d.out_bound = 0, None
-            if dx_bound is not None:
-                mark_planes(dx, dx_bound)
-            if link is not None:
-                link.pending -= 1
-                if link.pending > 0:        # other consumers of x follow: they accumulate into the same buffer
-                    link.buf, dx = dx, None
-                else:
-                    link.buf = None
-        if ctx.needs_input_grad[1]:
-            # wgrad is off the critical chain (only the optimiser needs it), so it runs on a side stream: the matrix-bound
-            # wgrad kernels then overlap the HBM-bound BatchNorm-backward kernels of the layers that follow on the main stream
-            side = _side_stream(x.device) if _runtime.side_stream_on() else None
-            tgt = _grad_target(w)
-
-            def launch_wgrad(side=side, tgt=tgt, x=x, dy=dy, w=w, w_k=w_k, d=d, dy_amax=dy_amax, x_amax=x_amax):   # bound now: it may run later
-                if side is not None:
-                    ev = torch.cuda.Event()      # recorded AFTER the dgrad launch: wgrad starts when the dgrad is done (letting it
-                    ev.record()                  # start next to the dgrad was measured 5 % slower, making every dgrad wait for the
-                                                 # previous wgrad 2 % slower)
-                    side.wait_event(ev)
-                    _keep_for_side(x.device, x, dy, w_k, dy_amax, x_amax)
-                with torch.cuda.stream(side) if side is not None else _nullcontext():
-                    sst = stream()
-                    nbytes = lib.pylc_conv2d_wgrad_workspace(C.byref(d))
-                    ws = _ws(nbytes, x.device)
-                    if cin_w % 4 == 0 and tgt is not None and side is None and _runtime.batch_slab_sums and nbytes > 0:
-                        # one queue: the split-K slabs stay in this weight's OWN workspace and every layer's slab sum runs in one launch
-                        # before the gradients are read (ops.flush_slab_sums, from sync_side_streams / the gradient bucketer)
-                        own = getattr(w, '_pylc_slab_ws', None)
-                        if own is not None and own.is_cuda and _core.slab_sum_pending(own.device, own):
-                            # the same weight again in this pass: sum its first slabs before they are overwritten -- or, when the second plan
-                            # needs a larger block, before the old block goes back to the allocator with a noted sum still pointing at it
-                            _core.flush_slab_sums(own.device)
-                        if own is None or own.numel() * 4 < nbytes or own.device != x.device:
-                            own = w._pylc_slab_ws = torch.empty(nbytes // 4 + 1, device=x.device)
-                        dwl = tgt
-                        pend = L.SlabSum()
-                        check(lib.pylc_conv2d_wgrad_slabs(C.byref(d), ptr(x), ptr(dy), ptr(dwl), ptr(own), nbytes, C.byref(pend), sst))
-                        if pend.splits > 0:
-                            _core.add_slab_sum(x.device, pend)
-                    elif cin_w % 4 == 0:
-                        dwl = tgt if tgt is not None else torch.empty((cout, r, s, cin), device=x.device).permute(0, 3, 1, 2)
-                        check(lib.pylc_conv2d_wgrad(C.byref(d), ptr(x), ptr(dy), ptr(dwl), None, ptr(ws), nbytes, sst))
-                    else:
-                        dw4 = torch.empty((cout, r, s, cin), device=x.device)
-                        check(lib.pylc_conv2d_wgrad(C.byref(d), ptr(x), ptr(dy), ptr(dw4), None, ptr(ws), nbytes, sst))
-                        dwl = tgt if tgt is not None else torch.empty((cout, r, s, cin_w), device=x.device).permute(0, 3, 1, 2)
-                        dwl.copy_(dw4[..., :cin_w].permute(0, 3, 1, 2))
-                if side is not None and tgt is None:
-                    torch.cuda.current_stream().wait_stream(side)      # the returned tensor is consumed by autograd on the main stream
-                return _deliver_grad(w, dwl)
-
-            hold = getattr(w, '_pylc_wgrad_hold', 0) if _runtime.wgrad_hold else 0
-            if hold and side is not None and tgt is not None:
-                # a layer-specific launch ORDER (set by the network, e.g. nets/deeplabv3p.py Decoder): this conv's wgrad fills every CU for
-                # milliseconds; started now it would sit in front of the short kernels that follow on the main queue (the 256->48 dgrad of
-                # decoder.py:27 waited 2 ms behind the 304->256 wgrad).  Held until `hold` further conv backwards have begun.
-                _defer_wgrad(x.device, launch_wgrad, hold)
-                dw = None
-            elif _runtime.defer_wgrad_1x1 and r * s == 1 and side is not None and tgt is not None:
-                # an HBM-heavy 1x1 wgrad started now would run beside the (HBM-bound) BatchNorm backward that follows on the main
-                # stream; held back until the NEXT conv backward begins, it runs beside that conv's matrix-bound dgrad instead
-                _defer_wgrad(x.device, launch_wgrad)
-                dw = None
-            else:
-                dw = launch_wgrad()
-        if has_bias and ctx.needs_input_grad[2] and getattr(dy, '_pylc_zero_colsum', False) and _runtime.skip_zero_bias_grad:
-            # dy was written by the backward of a TRAINING-mode BatchNorm that reads this conv's output directly (unet.py:112-118):
-            # dy = k (g - mean g - xhat mean(g xhat)) sums to ZERO over the rows of every channel (sum xhat = 0), i.e. the loss does not
-            # depend on a bias that the batch mean removes again.  What a column sum over dy -- or autograd in the reference -- returns
-            # here is the rounding noise of that cancellation (tests/golden: these keys are the fixtures' `zero_grad_keys`), so the pass
-            # over dy is skipped and the gradient is the exact value.  (SyncBN: the sum over ALL ranks' rows is zero, and the gradient
-            # all-reduce adds the ranks' bias gradients.)
-            tgt = _grad_target(bias)
-            if tgt is not None:
-                tgt.zero_()
-                db = _deliver_grad(bias, tgt)
-            else:
-                db = torch.zeros_like(bias)
-        elif has_bias and ctx.needs_input_grad[2]:
-            m = dy.shape[0] * dy.shape[2] * dy.shape[3]
-            cp = _r4(cout)
-            sums = torch.empty(2 * cp, device=x.device)
-            if dy_pl:       # per-channel sums straight from the planes (one read pass, as the fp32 form)
-                ws = torch.empty(lib.pylc_planes_colsum_workspace_floats(cout), device=x.device)
-                check(lib.pylc_planes_colsum(ptr(dy), cout, pstride(m, cout), nplanes(), ptr(planes_amax(dy)), m, cout, ptr(sums), ptr(ws), st))
-            else:
-                ws = torch.empty(lib.pylc_bn_workspace_floats(m, cp), device=x.device)
-                check(lib.pylc_bn_stats(ptr(dy), m, cp, yp, ptr(sums), ptr(ws), st))
-            tgt = _grad_target(bias)
-            if tgt is not None:
-                tgt.copy_(sums[:cout])
-                db = _deliver_grad(bias, tgt)
-            else:
-                db = sums[:cout].clone()
-        return dx, dw, db, None, None, None, None, None, None, None, None, None, None
+        return _adapt_back(ctx, conv2d_backward, dy)
 
 
 def conv2d(x, w, bias=None, stride=1, pad=0, dil=1, want_stats=False, res_link=None, out=None):
@@ -343,8 +340,7 @@ def conv2d(x, w, bias=None, stride=1, pad=0, dil=1, want_stats=False, res_link=N
     if ranges_needed():
         L.init()
         xa, wa = amax_of(x), weight_amax(w)
-    src = x.grad_fn if (torch.is_grad_enabled() and x.requires_grad) else None
-    bn_src = src if hasattr(src, 'bn_emit_ok') else None      # x is the output of a BatchNorm (BnActFn node: carries bn_emit_ok / sole)
+    bn_src = bn_node_of(x)
     if want_stats:
         res = Conv2dFn.apply(x, w, bias, stride, pad, dil, True, xa, wa, res_link, out, torch.is_grad_enabled(), bn_src)
         y, sums = res[0], res[1]
@@ -356,7 +352,7 @@ def conv2d(x, w, bias=None, stride=1, pad=0, dil=1, want_stats=False, res_link=N
     else:
         y = Conv2dFn.apply(x, w, bias, stride, pad, dil, False, xa, wa, res_link, out, torch.is_grad_enabled(), bn_src)
     fn = y.grad_fn
-    if fn is not None and getattr(fn, 'dy_pl_ok', False):
+    if fn is not None and fn.st.dy_pl_ok:
         y._pylc_dy_pl = True          # the BatchNorm that consumes y (its ONLY consumer, layers.conv_bn) may hand dy back as fp16 planes
     return y
 
@@ -421,16 +417,7 @@ class ConvTranspose2x2Fn(torch.autograd.Function):
             check(lib.pylc_conv2d_wgrad(C.byref(d), ptr(dy), ptr(x), ptr(dw), None, ptr(ws), nbytes, st))
             dw = _deliver_grad(w, dw)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            m = dy.shape[0] * dy.shape[2] * dy.shape[3]
-            sums = torch.empty(2 * cout, device=x.device)
-            wsb = torch.empty(lib.pylc_bn_workspace_floats(m, cout), device=x.device)
-            check(lib.pylc_bn_stats(ptr(dy), m, cout, pitch_of(dy), ptr(sums), ptr(wsb), st))
-            tgt = _grad_target(ctx.b_param)
-            if tgt is not None:
-                tgt.copy_(sums[:cout])
-                db = _deliver_grad(ctx.b_param, tgt)
-            else:
-                db = sums[:cout].clone()
+            db = bias_grad(ctx.b_param, dy, cout)
         return dx, dw, db
 
 
@@ -468,10 +455,8 @@ def conv_bn_act_eval_planes(x, w, bias, stride, pad, dil, coef, coef_ranges, res
         x_true = amax_of(x)                       # the producer's true maximum if it left one, else the scale bound itself
     yp = cout
     if into is not None:                  # fp32 result into channels [c0, c0 + Cout) of a caller-owned concat buffer (aspp.py:80, decoder.py:47)
-        buf, c0 = into[0][0], into[1]
-        if tuple(buf.shape[2:]) != (oh, ow) or buf.shape[0] != b or c0 % 4 or c0 + cout > buf.shape[1] or residual is not None:
-            raise L.PylcError('conv_bn_act_eval into=: slice [%d, %d) does not fit the %s buffer' % (c0, c0 + cout, tuple(buf.shape)))
-        y, yp, out_planes = buf[:, c0:c0 + cout], pitch_of(buf), False
+        y, yp = concat_slice(into, b, cout, oh, ow, 'conv_bn_act_eval', residual is None)
+        out_planes = False
     else:
         y = empty_nhwc(b, cout, oh, ow, x.device)
     d = _conv_desc(x, cin, cout, r, s, stride, pad, dil, cin, yp)
@@ -536,10 +521,7 @@ def conv_bn_act_eval(x, w, bias, stride, pad, dil, running_mean, running_var, ga
     b, _, h, wd = x.shape
     oh, ow = conv_out_size(h, r, stride, pad, dil), conv_out_size(wd, s, stride, pad, dil)
     if into is not None:
-        buf, c0 = into[0][0], into[1]
-        if tuple(buf.shape[2:]) != (oh, ow) or buf.shape[0] != b or c0 % 4 or cout % 4 or c0 + cout > buf.shape[1] or residual is not None:
-            raise L.PylcError('conv_bn_act_eval into=: slice [%d, %d) does not fit the %s buffer' % (c0, c0 + cout, tuple(buf.shape)))
-        y, yp = buf[:, c0:c0 + cout], pitch_of(buf)
+        y, yp = concat_slice(into, b, cout, oh, ow, 'conv_bn_act_eval', cout % 4 == 0 and residual is None)
     else:
         yp = _r4(cout)
         y = empty_nhwc(b, cout, oh, ow, x.device, yp)

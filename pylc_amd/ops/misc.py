@@ -3,50 +3,70 @@ from . import _core
 from ._core import *      # noqa: F401,F403  (layout / planes / range / stream helpers, lib bindings, torch)
 
 
+# Every operator below is a pair of plain driver functions -- forward(needs_input_grad, arguments) -> (outputs, tensors to save, backward-state
+# record, non-differentiable outputs); backward(record, saved tensors, needs_input_grad, gradient) -> gradients of the leading arguments --
+# and a Function that only adapts them to autograd (_core._adapt / _adapt_back).  pylc_amd.torch_ops calls the drivers directly.
+def relu_forward(needs, x):
+    L.init()
+    x = as_nhwc(x)
+    b, c, h, w = x.shape
+    out = empty_nhwc(b, c, h, w, x.device)
+    check(lib.pylc_relu_fwd(ptr(x), pitch_of(x), ptr(out), c, b * h * w, c, stream()))
+    return out, (out,), None, ()           # the backward reads the saved output alone: no record
+
+
+def relu_backward(state, saved, needs, dout):
+    (out,) = saved
+    dout = as_nhwc(dout)
+    b, c, h, w = out.shape
+    dx = empty_nhwc(b, c, h, w, out.device)
+    check(lib.pylc_relu_bwd(ptr(dout), pitch_of(dout), ptr(out), c, ptr(dx), c, b * h * w, c, stream()))
+    return (dx,)
+
+
 class ReluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        L.init()
-        x = as_nhwc(x)
-        b, c, h, w = x.shape
-        out = empty_nhwc(b, c, h, w, x.device)
-        check(lib.pylc_relu_fwd(ptr(x), pitch_of(x), ptr(out), c, b * h * w, c, stream()))
-        ctx.save_for_backward(out)
-        return out
+        return _adapt(ctx, relu_forward(ctx.needs_input_grad, x))
 
     @staticmethod
     def backward(ctx, dout):
-        (out,) = ctx.saved_tensors
-        dout = as_nhwc(dout)
-        b, c, h, w = out.shape
-        dx = empty_nhwc(b, c, h, w, out.device)
-        check(lib.pylc_relu_bwd(ptr(dout), pitch_of(dout), ptr(out), c, ptr(dx), c, b * h * w, c, stream()))
-        return dx
+        return _adapt_back(ctx, relu_backward, dout)
 
 
 def relu(x):
     return ReluFn.apply(x)
 
 
+class DropoutState:
+    __slots__ = ('p', 'seed')
+
+    def __init__(self, p, seed):
+        self.p, self.seed = p, seed
+
+
+def dropout_forward(needs, x, p, seed):
+    """The dropout mask is a function of the seed: the backward is the same pass over the gradient."""
+    L.init()
+    x = as_nhwc(x)
+    b, c, h, w = x.shape
+    out = empty_nhwc(b, c, h, w, x.device)
+    check(lib.pylc_dropout(ptr(x), pitch_of(x), ptr(out), c, b * h * w, c, p, seed, stream()))
+    return out, (), DropoutState(p, seed), ()
+
+
+def dropout_backward(state, saved, needs, dout):
+    return (dropout_forward(needs, dout, state.p, state.seed)[0],)
+
+
 class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, seed):
-        L.init()
-        x = as_nhwc(x)
-        b, c, h, w = x.shape
-        out = empty_nhwc(b, c, h, w, x.device)
-        check(lib.pylc_dropout(ptr(x), pitch_of(x), ptr(out), c, b * h * w, c, p, seed, stream()))
-        ctx.cfg = (p, seed)
-        return out
+        return _adapt(ctx, dropout_forward(ctx.needs_input_grad, x, p, seed))
 
     @staticmethod
     def backward(ctx, dout):
-        p, seed = ctx.cfg
-        dout = as_nhwc(dout)
-        b, c, h, w = dout.shape
-        dx = empty_nhwc(b, c, h, w, dout.device)
-        check(lib.pylc_dropout(ptr(dout), pitch_of(dout), ptr(dx), c, b * h * w, c, p, seed, stream()))
-        return dx, None, None
+        return _adapt_back(ctx, dropout_backward, dout)
 
 
 def dropout(x, p, seed):
@@ -62,50 +82,64 @@ def dropout(x, p, seed):
 # ----------------------------------------------------------------------------------------------
 # pooling / resize
 # ----------------------------------------------------------------------------------------------
+class PoolState:
+    """cfg: (b, c, h, w, k, stride, pad, oh, ow); link: the gradient link of x when a skip connection may park its crop gradient on it."""
+    __slots__ = ('cfg', 'link')
+
+    def __init__(self, cfg, link=None):
+        self.cfg, self.link = cfg, link
+
+
+def maxpool_forward(needs, x, k, stride, pad, link=None, planes_bound=None):
+    """Saves the uint8 argmax indices (None when x takes no gradient)."""
+    L.init()
+    x = as_nhwc(x)
+    if pitch_of(x) != x.shape[1]:
+        x = x.contiguous(memory_format=torch.channels_last)
+    b, c, h, w = x.shape
+    oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    y = empty_nhwc(b, c, oh, ow, x.device)
+    idx = torch.empty((b, oh, ow, c), device=x.device, dtype=torch.uint8) if needs[0] else None
+    if planes_bound is not None:       # the pooled tensor as fp16 planes (its only reader is a conv that takes them)
+        check(lib.pylc_maxpool_fwd_planes(ptr(x), ptr(y), pstride(b * oh * ow, c), nplanes(), ptr(planes_bound), ptr(idx), b, h, w, c, k, stride, pad,
+                                          oh, ow, stream()))
+    else:
+        check(lib.pylc_maxpool_fwd(ptr(x), ptr(y), ptr(idx), b, h, w, c, k, stride, pad, oh, ow, stream()))
+    link = link if needs[0] else None
+    if link is not None:
+        link.pool_armed = True
+    return y, (idx,), PoolState((b, c, h, w, k, stride, pad, oh, ow), link), ()
+
+
+def maxpool_backward(state, saved, needs, dy):
+    (idx,) = saved
+    b, c, h, w, k, stride, pad, oh, ow = state.cfg
+    dy = as_nhwc(dy)
+    if pitch_of(dy) != c:
+        dy = dy.contiguous(memory_format=torch.channels_last)
+    dx = empty_nhwc(b, c, h, w, dy.device)
+    link = state.link
+    crop = None
+    if link is not None:
+        link.pool_armed = False
+        crop, link.crop = link.crop, None
+    if crop is not None:        # the skip connection's gradient (centre crop) is summed in the same pass
+        g, c0, h0, w0 = crop
+        check(lib.pylc_maxpool_bwd_add(ptr(dy), ptr(idx), ptr(dx), b, h, w, c, k, stride, pad, oh, ow, g.data_ptr() + 4 * c0, pitch_of(g),
+                                       h0, w0, g.shape[2], g.shape[3], stream()))
+    else:
+        check(lib.pylc_maxpool_bwd(ptr(dy), ptr(idx), ptr(dx), b, h, w, c, k, stride, pad, oh, ow, stream()))
+    return (dx,)
+
+
 class MaxPoolFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, k, stride, pad, link=None, planes_bound=None):
-        L.init()
-        x = as_nhwc(x)
-        if pitch_of(x) != x.shape[1]:
-            x = x.contiguous(memory_format=torch.channels_last)
-        b, c, h, w = x.shape
-        oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-        y = empty_nhwc(b, c, oh, ow, x.device)
-        need_idx = ctx.needs_input_grad[0]
-        idx = torch.empty((b, oh, ow, c), device=x.device, dtype=torch.uint8) if need_idx else None
-        if planes_bound is not None:       # the pooled tensor as fp16 planes (its only reader is a conv that takes them)
-            check(lib.pylc_maxpool_fwd_planes(ptr(x), ptr(y), pstride(b * oh * ow, c), nplanes(), ptr(planes_bound), ptr(idx), b, h, w, c, k, stride, pad,
-                                              oh, ow, stream()))
-        else:
-            check(lib.pylc_maxpool_fwd(ptr(x), ptr(y), ptr(idx), b, h, w, c, k, stride, pad, oh, ow, stream()))
-        ctx.save_for_backward(idx)
-        ctx.cfg = (b, c, h, w, k, stride, pad, oh, ow)
-        ctx.link = link if need_idx else None
-        if ctx.link is not None:
-            link.pool_armed = True
-        return y
+    def forward(ctx, *args):
+        return _adapt(ctx, maxpool_forward(ctx.needs_input_grad, *args))
 
     @staticmethod
     def backward(ctx, dy):
-        (idx,) = ctx.saved_tensors
-        b, c, h, w, k, stride, pad, oh, ow = ctx.cfg
-        dy = as_nhwc(dy)
-        if pitch_of(dy) != c:
-            dy = dy.contiguous(memory_format=torch.channels_last)
-        dx = empty_nhwc(b, c, h, w, dy.device)
-        link = ctx.link
-        crop = None
-        if link is not None:
-            link.pool_armed = False
-            crop, link.crop = link.crop, None
-        if crop is not None:        # the skip connection's gradient (centre crop) is summed in the same pass
-            g, c0, h0, w0 = crop
-            check(lib.pylc_maxpool_bwd_add(ptr(dy), ptr(idx), ptr(dx), b, h, w, c, k, stride, pad, oh, ow, g.data_ptr() + 4 * c0, pitch_of(g),
-                                           h0, w0, g.shape[2], g.shape[3], stream()))
-        else:
-            check(lib.pylc_maxpool_bwd(ptr(dy), ptr(idx), ptr(dx), b, h, w, c, k, stride, pad, oh, ow, stream()))
-        return dx, None, None, None, None, None
+        return _adapt_back(ctx, maxpool_backward, dy)
 
 
 def maxpool(x, k, stride, pad=0, link=None, out_planes=False):
@@ -258,48 +292,62 @@ def concat_slices(holder, parts):
     return out
 
 
+class ShapeState:
+    """The record of a node whose backward needs the input's shape alone (BilinearFn, GapFn): shape = (b, c, h, w); GapFn: the armed gradient
+    link of x."""
+    __slots__ = ('shape', 'res_link')
+
+    def __init__(self, shape, res_link=None):
+        self.shape, self.res_link = shape, res_link
+
+
+def bilinear_forward(needs, x, oh, ow, into=None):
+    L.init()
+    x = as_nhwc(x)
+    b, c, h, w = x.shape
+    cp = pitch_of(x)
+    cc = _r4(c)
+    if cc > cp:
+        raise L.PylcError('bilinear: channel count %d needs a pitch >= %d' % (c, cc))
+    if into is not None:               # channels [c0, c0 + c) of a concat buffer: into = ([buffer], c0)
+        y, yp = concat_slice(into, b, c, oh, ow, 'bilinear', c % 4 == 0)
+    else:
+        y, yp = empty_nhwc(b, c, oh, ow, x.device, cc), cc
+    check(lib.pylc_bilinear_fwd(ptr(x), cp, ptr(y), yp, b, h, w, cc, oh, ow, stream()))
+    return y, (), ShapeState((b, c, h, w)), ()
+
+
+def bilinear_backward(state, saved, needs, dy):
+    b, c, h, w = state.shape
+    oh, ow = dy.shape[2:]
+    dy = as_nhwc(dy)
+    cc = _r4(c)
+    if pitch_of(dy) < cc:
+        t = zeros_nhwc(b, c, oh, ow, dy.device, cc)
+        t.copy_(dy)
+        dy = t
+    dx = empty_nhwc(b, c, h, w, dy.device, cc)
+    if oh >= 2 * h and ow >= 2 * w:      # up-sampling: one axis at a time (10 + 10 instead of 100 candidate taps per element at x4)
+        tmp = torch.empty(lib.pylc_bilinear_bwd_workspace(b, w, cc, oh) // 4, device=dy.device, dtype=torch.float32)
+        amax = torch.empty(1, dtype=torch.int32, device=dy.device) if ranges_needed() and _runtime.fused_grad_ranges else None
+        check(lib.pylc_bilinear_bwd_separable(ptr(dy), pitch_of(dy), ptr(dx), cc, b, h, w, cc, oh, ow, ptr(tmp), ptr(amax), stream()))
+        if amax is not None:
+            tag_amax(dx, amax)
+    else:
+        check(lib.pylc_bilinear_bwd(ptr(dy), pitch_of(dy), ptr(dx), cc, b, h, w, cc, oh, ow, stream()))
+    return (dx,)
+
+
 class BilinearFn(torch.autograd.Function):
     """F.interpolate(mode='bilinear', align_corners=True) to an explicit output size."""
 
     @staticmethod
-    def forward(ctx, x, oh, ow, into=None):
-        L.init()
-        x = as_nhwc(x)
-        b, c, h, w = x.shape
-        cp = pitch_of(x)
-        cc = _r4(c)
-        if cc > cp:
-            raise L.PylcError('bilinear: channel count %d needs a pitch >= %d' % (c, cc))
-        if into is not None:               # channels [c0, c0 + c) of a concat buffer: into = ([buffer], c0)
-            buf, c0 = into[0][0], into[1]
-            if tuple(buf.shape[2:]) != (oh, ow) or buf.shape[0] != b or c0 % 4 or c % 4 or c0 + c > buf.shape[1]:
-                raise L.PylcError('bilinear into=: slice [%d, %d) does not fit the %s buffer' % (c0, c0 + c, tuple(buf.shape)))
-            y, yp = buf[:, c0:c0 + c], pitch_of(buf)
-        else:
-            y, yp = empty_nhwc(b, c, oh, ow, x.device, cc), cc
-        check(lib.pylc_bilinear_fwd(ptr(x), cp, ptr(y), yp, b, h, w, cc, oh, ow, stream()))
-        ctx.cfg = (b, c, h, w, oh, ow)
-        return y
+    def forward(ctx, *args):
+        return _adapt(ctx, bilinear_forward(ctx.needs_input_grad, *args))
 
     @staticmethod
     def backward(ctx, dy):
-        b, c, h, w, oh, ow = ctx.cfg
-        dy = as_nhwc(dy)
-        cc = _r4(c)
-        if pitch_of(dy) < cc:
-            t = zeros_nhwc(b, c, oh, ow, dy.device, cc)
-            t.copy_(dy)
-            dy = t
-        dx = empty_nhwc(b, c, h, w, dy.device, cc)
-        if oh >= 2 * h and ow >= 2 * w:      # up-sampling: one axis at a time (10 + 10 instead of 100 candidate taps per element at x4)
-            tmp = torch.empty(lib.pylc_bilinear_bwd_workspace(b, w, cc, oh) // 4, device=dy.device, dtype=torch.float32)
-            amax = torch.empty(1, dtype=torch.int32, device=dy.device) if ranges_needed() and _runtime.fused_grad_ranges else None
-            check(lib.pylc_bilinear_bwd_separable(ptr(dy), pitch_of(dy), ptr(dx), cc, b, h, w, cc, oh, ow, ptr(tmp), ptr(amax), stream()))
-            if amax is not None:
-                tag_amax(dx, amax)
-        else:
-            check(lib.pylc_bilinear_bwd(ptr(dy), pitch_of(dy), ptr(dx), cc, b, h, w, cc, oh, ow, stream()))
-        return dx, None, None, None
+        return _adapt_back(ctx, bilinear_backward, dy)
 
 
 def bilinear(x, oh, ow, into=None):
@@ -307,41 +355,39 @@ def bilinear(x, oh, ow, into=None):
     return inherit_amax(y, x) if ranges_needed() else y       # interpolation weights are a convex combination
 
 
+def gap_forward(needs, x, res_link=None):
+    L.init()
+    b, c, h, w = x.shape
+    y = empty_nhwc(b, c, 1, 1, x.device)
+    if is_planes(x) and c % 8 == 0 and _runtime.gap_planes:
+        # the backbone's last BatchNorm left fp16 planes for the atrous convs: pool them as they are (same bits as converting first)
+        check(lib.pylc_gap_fwd_planes(ptr(x), pstride(b * h * w, c), nplanes(), ptr(planes_amax(x)), ptr(y), b, h * w, c, stream()))
+    else:
+        x = as_nhwc(x)
+        if pitch_of(x) != x.shape[1]:
+            x = x.contiguous(memory_format=torch.channels_last)
+        check(lib.pylc_gap_fwd(ptr(x), ptr(y), b, h * w, c, stream()))
+    return y, (), ShapeState((b, c, h, w), res_link.arm() if (res_link is not None and needs[0]) else None), ()
+
+
+def gap_backward(state, saved, needs, dy):
+    b, c, h, w = state.shape
+    dy = dy.reshape(b, c).contiguous()
+    link = state.res_link
+    sink = _link_sink(link)
+    dx = sink if sink is not None else empty_nhwc(b, c, h, w, dy.device)
+    check(lib.pylc_gap_bwd_acc(ptr(dy), ptr(dx), b, h * w, c, 1 if sink is not None else 0, stream()))
+    return (link.hand_over(dx) if link is not None else dx,)
+
+
 class GapFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, res_link=None):
-        L.init()
-        b, c, h, w = x.shape
-        y = empty_nhwc(b, c, 1, 1, x.device)
-        if is_planes(x) and c % 8 == 0 and _runtime.gap_planes:
-            # the backbone's last BatchNorm left fp16 planes for the atrous convs: pool them as they are (same bits as converting first)
-            check(lib.pylc_gap_fwd_planes(ptr(x), pstride(b * h * w, c), nplanes(), ptr(planes_amax(x)), ptr(y), b, h * w, c, stream()))
-        else:
-            x = as_nhwc(x)
-            if pitch_of(x) != x.shape[1]:
-                x = x.contiguous(memory_format=torch.channels_last)
-            check(lib.pylc_gap_fwd(ptr(x), ptr(y), b, h * w, c, stream()))
-        ctx.cfg = (b, c, h, w)
-        ctx.res_link = res_link if (res_link is not None and ctx.needs_input_grad[0]) else None
-        if ctx.res_link is not None:
-            res_link.pending += 1           # one more backward node that adds its part of x's gradient into the shared buffer
-        return y
+    def forward(ctx, *args):
+        return _adapt(ctx, gap_forward(ctx.needs_input_grad, *args))
 
     @staticmethod
     def backward(ctx, dy):
-        b, c, h, w = ctx.cfg
-        dy = dy.reshape(b, c).contiguous()
-        link = ctx.res_link
-        sink = _link_sink(link)
-        dx = sink if sink is not None else empty_nhwc(b, c, h, w, dy.device)
-        check(lib.pylc_gap_bwd_acc(ptr(dy), ptr(dx), b, h * w, c, 1 if sink is not None else 0, stream()))
-        if link is not None:
-            link.pending -= 1
-            if link.pending > 0:            # the convs that read x follow: their dgrads accumulate into the same buffer
-                link.buf, dx = dx, None
-            else:
-                link.buf = None
-        return dx, None
+        return _adapt_back(ctx, gap_backward, dy)
 
 
 def global_avg_pool(x, res_link=None):
@@ -457,106 +503,114 @@ class MultiLossFn(torch.autograd.Function):
     NO_IGNORE = -2 ** 31
 
     @staticmethod
-    def forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index=None, bad=None, pixel_weights=None):
-        L.init()
-        logits = as_nhwc(logits)
-        b, c, h, w = logits.shape
-        n = b * h * w
-        target = target.contiguous()
-        if pixel_weights is not None:
-            if (not torch.is_tensor(pixel_weights) or pixel_weights.dtype != torch.float32 or tuple(pixel_weights.shape) != (b, h, w)
-                    or pixel_weights.device != logits.device):
-                raise L.PylcError('pixel_weights must be float32 [B,H,W] matching the logits, on their device')
-            pixel_weights = pixel_weights.detach().contiguous()
-            if ignore_index is None:
-                ignore_index = MultiLossFn.NO_IGNORE
-        ctx.ignore = ignore_index
-        if ignore_index is not None:
-            return MultiLossFn._forward_ignore(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, int(ignore_index), bad,
-                                               pixel_weights)
-        if target.dtype != torch.int64 or tuple(target.shape) != (b, h, w):
-            raise L.PylcError('target must be int64 [B,H,W] matching the logits')
-        dev = logits.device
-        st = stream()
-        k = 3 + 3 * c
-        # data parallel: two more floats ride on the statistics message -- this rank's tile count b and b^2 -- so that unequal shards are
-        # DETECTED without a collective of their own (sum b^2 * world == (sum b)^2 iff all equal; Model.train checks the reduced pair at its
-        # report interval).  A separate all_gather triggered by a rank-local condition would desynchronise the ranks' collective sequences
-        # in exactly the case it is meant to catch.
-        stats = torch.empty(k + (2 if group is not None else 0), device=dev)
-        ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
-        check(lib.pylc_multiloss_stats(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(class_weights), ptr(stats), ptr(ws), st))
-        n_global = float(n)
-        if group is not None:
-            stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
-            _runtime.sync_all_reduce(stats, group)   # Dice / weighted CE are not shard-decomposable
-            n_global = float(n) * dist.get_world_size(group)
-            note_shard_pair(stats[k:], dist.get_world_size(group))
-        losses = torch.empty(4, device=dev)
-        check(lib.pylc_multiloss_finalize(ptr(stats), n_global, c, w_ce, w_dice, w_focal, ptr(losses), st))
-        ctx.save_for_backward(logits, target, stats, class_weights)
-        ctx.cfg = (n_global, w_ce, w_dice, w_focal, group)
-        return losses
-
-    @staticmethod
-    def _forward_ignore(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights=None):
-        b, c, h, w = logits.shape
-        n = b * h * w
-        if target.dtype not in (torch.uint8, torch.int64) or tuple(target.shape) != (b, h, w):
-            raise L.PylcError('target must be uint8 or int64 [B,H,W] matching the logits')
-        if bad is not None and (bad.dtype != torch.int64 or bad.numel() != 1 or bad.device != logits.device):
-            raise L.PylcError('bad must be an int64 [1] tensor on the device of the logits')
-        dev = logits.device
-        st = stream()
-        k = 3 + 3 * c
-        stats = torch.empty(k + (2 if group is not None else 0), device=dev)         # (the shard pair rides along as on the plain path)
-        ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
-        if pixel_weights is None:
-            check(lib.pylc_multiloss_stats_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
-                                              ptr(class_weights), ptr(stats), ptr(ws), ptr(bad), st))
-        else:
-            check(lib.pylc_multiloss_stats_w(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
-                                             ptr(class_weights), ptr(pixel_weights), ptr(stats), ptr(ws), ptr(bad), st))
-        if group is not None:
-            stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
-            _runtime.sync_all_reduce(stats, group)
-            note_shard_pair(stats[k:], dist.get_world_size(group))
-        losses = torch.empty(4, device=dev)
-        check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))      # n_valid (sum u): from the reduced class counts
-        if pixel_weights is None:
-            ctx.save_for_backward(logits, target, stats, class_weights)
-        else:
-            ctx.save_for_backward(logits, target, stats, class_weights, pixel_weights)
-        ctx.cfg = (None, w_ce, w_dice, w_focal, group)
-        return losses
+    def forward(ctx, *args):
+        return _adapt(ctx, multiloss_forward(ctx.needs_input_grad, *args))
 
     @staticmethod
     def backward(ctx, dlosses):
-        saved = ctx.saved_tensors
-        logits, target, stats, cw = saved[:4]
-        pw = saved[4] if len(saved) > 4 else None
-        n_global, w_ce, w_dice, w_focal, group = ctx.cfg
-        b, c, h, w = logits.shape
-        n = b * h * w
-        # the loss is already the GLOBAL loss; each rank back-propagates its own pixels' share and the
-        # gradient all-reduce SUMS the shares (pylc_amd/parallel.py)
-        gs = dlosses[0:1].contiguous().float()
-        cp = _r4(c)
-        dl = empty_nhwc(b, c, h, w, logits.device, cp)
-        amax = torch.empty(1, dtype=torch.int32, device=logits.device) if ranges_needed() and _runtime.fused_grad_ranges else None
-        ignore = getattr(ctx, 'ignore', None)
-        if ignore is None:
-            check(lib.pylc_multiloss_bwd(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(cw), ptr(stats), n_global,
-                                         w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
-        elif pw is None:
-            check(lib.pylc_multiloss_bwd_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw),
-                                            ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
-        else:
-            check(lib.pylc_multiloss_bwd_w(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw),
-                                           ptr(pw), ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
-        if amax is not None:
-            tag_amax(dl, amax)              # (read by a conv backward directly when the net has no logits up-sampling: the U-Net)
-        return dl, None, None, None, None, None, None, None, None, None
+        return _adapt_back(ctx, multiloss_backward, dlosses)
+
+
+class LossState:
+    """cfg: (n_global or None, w_ce, w_dice, w_focal, group); ignore: the ignore label the kernels ran with (None: the plain path)."""
+    __slots__ = ('cfg', 'ignore')
+
+    def __init__(self, cfg, ignore=None):
+        self.cfg, self.ignore = cfg, ignore
+
+
+def multiloss_forward(needs, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index=None, bad=None, pixel_weights=None):
+    """Saves (logits, target, stats, class_weights[, pixel_weights])."""
+    L.init()
+    logits = as_nhwc(logits)
+    b, c, h, w = logits.shape
+    n = b * h * w
+    target = target.contiguous()
+    if pixel_weights is not None:
+        if (not torch.is_tensor(pixel_weights) or pixel_weights.dtype != torch.float32 or tuple(pixel_weights.shape) != (b, h, w)
+                or pixel_weights.device != logits.device):
+            raise L.PylcError('pixel_weights must be float32 [B,H,W] matching the logits, on their device')
+        pixel_weights = pixel_weights.detach().contiguous()
+        if ignore_index is None:
+            ignore_index = MultiLossFn.NO_IGNORE
+    if ignore_index is not None:
+        return _multiloss_forward_ignore(logits, target, class_weights, w_ce, w_dice, w_focal, group, int(ignore_index), bad, pixel_weights)
+    if target.dtype != torch.int64 or tuple(target.shape) != (b, h, w):
+        raise L.PylcError('target must be int64 [B,H,W] matching the logits')
+    dev = logits.device
+    st = stream()
+    k = 3 + 3 * c
+    # data parallel: two more floats ride on the statistics message -- this rank's tile count b and b^2 -- so that unequal shards are
+    # DETECTED without a collective of their own (sum b^2 * world == (sum b)^2 iff all equal; Model.train checks the reduced pair at its
+    # report interval).  A separate all_gather triggered by a rank-local condition would desynchronise the ranks' collective sequences
+    # in exactly the case it is meant to catch.
+    stats = torch.empty(k + (2 if group is not None else 0), device=dev)
+    ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
+    check(lib.pylc_multiloss_stats(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(class_weights), ptr(stats), ptr(ws), st))
+    n_global = float(n)
+    if group is not None:
+        stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
+        _runtime.sync_all_reduce(stats, group)   # Dice / weighted CE are not shard-decomposable (SURVEY 8e)
+        n_global = float(n) * dist.get_world_size(group)
+        note_shard_pair(stats[k:], dist.get_world_size(group))
+    losses = torch.empty(4, device=dev)
+    check(lib.pylc_multiloss_finalize(ptr(stats), n_global, c, w_ce, w_dice, w_focal, ptr(losses), st))
+    return losses, (logits, target, stats, class_weights), LossState((n_global, w_ce, w_dice, w_focal, group)), ()
+
+
+def _multiloss_forward_ignore(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights=None):
+    b, c, h, w = logits.shape
+    n = b * h * w
+    if target.dtype not in (torch.uint8, torch.int64) or tuple(target.shape) != (b, h, w):
+        raise L.PylcError('target must be uint8 or int64 [B,H,W] matching the logits')
+    if bad is not None and (bad.dtype != torch.int64 or bad.numel() != 1 or bad.device != logits.device):
+        raise L.PylcError('bad must be an int64 [1] tensor on the device of the logits')
+    dev = logits.device
+    st = stream()
+    k = 3 + 3 * c
+    stats = torch.empty(k + (2 if group is not None else 0), device=dev)         # (the shard pair rides along as on the plain path)
+    ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
+    if pixel_weights is None:
+        check(lib.pylc_multiloss_stats_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
+                                          ptr(class_weights), ptr(stats), ptr(ws), ptr(bad), st))
+    else:
+        check(lib.pylc_multiloss_stats_w(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
+                                         ptr(class_weights), ptr(pixel_weights), ptr(stats), ptr(ws), ptr(bad), st))
+    if group is not None:
+        stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
+        _runtime.sync_all_reduce(stats, group)
+        note_shard_pair(stats[k:], dist.get_world_size(group))
+    losses = torch.empty(4, device=dev)
+    check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))      # n_valid (sum u): from the reduced class counts
+    saved = (logits, target, stats, class_weights) + (() if pixel_weights is None else (pixel_weights,))
+    return losses, saved, LossState((None, w_ce, w_dice, w_focal, group), ignore_index), ()
+
+
+def multiloss_backward(state, saved, needs, dlosses):
+    logits, target, stats, cw = saved[:4]
+    pw = saved[4] if len(saved) > 4 else None
+    n_global, w_ce, w_dice, w_focal, group = state.cfg
+    b, c, h, w = logits.shape
+    n = b * h * w
+    # the loss is already the GLOBAL loss; each rank back-propagates its own pixels' share and the
+    # gradient all-reduce SUMS the shares (pylc_amd/parallel.py)
+    gs = dlosses[0:1].contiguous().float()
+    cp = _r4(c)
+    dl = empty_nhwc(b, c, h, w, logits.device, cp)
+    amax = torch.empty(1, dtype=torch.int32, device=logits.device) if ranges_needed() and _runtime.fused_grad_ranges else None
+    ignore = state.ignore
+    if ignore is None:
+        check(lib.pylc_multiloss_bwd(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(cw), ptr(stats), n_global,
+                                     w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
+    elif pw is None:
+        check(lib.pylc_multiloss_bwd_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw),
+                                        ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
+    else:
+        check(lib.pylc_multiloss_bwd_w(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw),
+                                       ptr(pw), ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
+    if amax is not None:
+        tag_amax(dl, amax)              # (read by a conv backward directly when the net has no logits up-sampling: the U-Net)
+    return (dl,)
 
 
 def multiloss(logits, target, class_weights, w_ce, w_dice, w_focal, group=None, ignore_index=None, bad=None, pixel_weights=None):

@@ -5,8 +5,8 @@ call `F.conv2d` / `nn.BatchNorm2d` / `F.interpolate` / `MultiLoss.forward` today
 
 The operators are the plain functional forms -- tensors in, fresh tensors out, no hidden state: they run the same kernels as
 pylc_amd.ops (whose autograd.Functions additionally carry the in-network fusions: gradient links, concat buffers, fp16-plane
-activations, flat-arena gradients) by driving those Functions' forward / backward with a stand-in context.  Importing this module
-registers them (pylc_amd/__init__.py does).
+activations, flat-arena gradients) by calling the plain driver functions those Functions adapt to autograd (ops.conv2d_forward /
+ops.conv2d_backward, ...) with a backward-state record built here.  Importing this module registers them (pylc_amd/__init__.py does).
 
     y   = torch.ops.pylc_hip.conv2d(x, w, None, 1, 1, 1)              # any layout in, NHWC-memory tensor out, differentiable
     out = torch.ops.pylc_hip.batch_norm_act(y, g, b, rm, rv, None, True, True, 1e-5, 0.1)
@@ -18,27 +18,6 @@ from torch import Tensor
 
 from . import ops
 from . import lib as L
-
-
-class _Ctx:
-    """What ops.*Fn.forward / backward need from an autograd context."""
-
-    def __init__(self, needs):
-        self.needs_input_grad = tuple(needs)
-        self._saved = ()
-
-    def save_for_backward(self, *tensors):
-        self._saved = tensors
-
-    @property
-    def saved_tensors(self):
-        return self._saved
-
-    def set_materialize_grads(self, value):
-        pass
-
-    def mark_non_differentiable(self, *tensors):
-        pass
 
 
 def _none_if_empty(t):
@@ -66,11 +45,10 @@ def _fake_nhwc(like, b, c, h, w, pitch=None):
 @torch.library.custom_op('pylc_hip::conv2d', mutates_args=())
 def conv2d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, padding: int, dilation: int) -> Tensor:
     L.init()
-    ctx = _Ctx((False, False, False))
     xa = wa = None
     if ops.ranges_needed():
         xa, wa = ops.amax_of(ops.as_nhwc(x)), ops.weight_amax(weight)
-    return ops.Conv2dFn.forward(ctx, x, weight, bias, stride, padding, dilation, False, xa, wa, None, None, False)
+    return ops.conv2d_forward((False, False, False), x, weight, bias, stride, padding, dilation, False, xa, wa)[0]
 
 
 @conv2d.register_fake
@@ -84,26 +62,16 @@ def _(x, weight, bias, stride, padding, dilation):
 def conv2d_backward(dy: Tensor, x: Tensor, weight: Tensor, stride: int, padding: int, dilation: int, has_bias: bool,
                     need_dx: bool, need_dw: bool) -> Tuple[Tensor, Tensor, Tensor]:
     L.init()
-    ctx = _Ctx((need_dx, need_dw, has_bias))
     x = ops.as_nhwc(x)
-    cout, cin_w, r, s = weight.shape
-    w_k = weight
-    if cin_w % 4 != 0:               # thin-input stem: the KRSC rows zero-padded to the 4-channel pack (as ops.Conv2dFn.forward)
-        w_k = torch.zeros((cout, r, s, x.shape[1]), device=weight.device, dtype=torch.float32)
-        w_k[..., :cin_w] = weight.detach().permute(0, 2, 3, 1)
-    ctx.save_for_backward(x, w_k)
-    ctx.geom = (stride, padding, dilation, cin_w, has_bias)
+    cout, cin_w = weight.shape[:2]
     # functional operator: gradients come back as FRESH tensors.  A parameter of a built Model carries its flat-arena gradient view
-    # (`_pylc_grad`), which Conv2dFn.backward would write into and then return nothing -- so the stand-in context sees a detached alias
+    # (`_pylc_grad`), which ops.conv2d_backward would write into and then return nothing -- so the record holds a detached alias
     # (a new Python object without the arena attributes), never the parameter itself
     wp = weight.detach()
-    if w_k is weight:
-        w_k = wp
-    ctx.save_for_backward(x, w_k)
-    ctx.w_param, ctx.b_param = wp, (weight.new_empty(cout) if has_bias else None)
-    ctx.ranges = (ops.amax_of(x), ops.weight_amax(weight)) if ops.ranges_needed() else (None, None)
-    ctx.x_pl, ctx.dy_pl_ok, ctx.res_link, ctx.bn_src = False, False, None, None
-    dx, dw, db = ops.Conv2dFn.backward(ctx, dy)[:3]
+    w_k = wp if cin_w % 4 == 0 else ops.pad_stem_filter(weight, x.shape[1])      # thin-input stem: x is the 4-channel pack
+    state = ops.ConvState((stride, padding, dilation, cin_w, has_bias), wp, weight.new_empty(cout) if has_bias else None,
+                          (ops.amax_of(x), ops.weight_amax(weight)) if ops.ranges_needed() else (None, None))
+    dx, dw, db = ops.conv2d_backward(state, (x, w_k), (need_dx, need_dw, has_bias), dy)
     ops.sync_side_streams()          # the wgrad ran on the side stream: the returned tensors are consumed on this one
     if dw is not None:
         dw = dw.contiguous(memory_format=torch.channels_last) if dw.dim() == 4 else dw
@@ -138,7 +106,7 @@ torch.library.register_autograd('pylc_hip::conv2d', _conv2d_bwd, setup_context=_
 # ------------------------------------------------------------------------------------------------------------------------------
 @torch.library.custom_op('pylc_hip::dwconv3x3', mutates_args=())
 def dwconv3x3(x: Tensor, weight: Tensor, stride: int, dilation: int) -> Tensor:
-    return ops.DwConv3x3Fn.forward(_Ctx((False, False)), x, weight, stride, dilation, None, False)[0]
+    return ops.dwconv3x3_forward((False, False), x, weight, stride, dilation)[0][0]
 
 
 @dwconv3x3.register_fake
@@ -149,13 +117,8 @@ def _(x, weight, stride, dilation):
 
 @torch.library.custom_op('pylc_hip::dwconv3x3_backward', mutates_args=())
 def dwconv3x3_backward(dy: Tensor, x: Tensor, weight: Tensor, stride: int, dilation: int) -> Tuple[Tensor, Tensor]:
-    ctx = _Ctx((True, True))
-    ctx.save_for_backward(ops.as_nhwc(x), None, None, None)
-    ctx.bn_relu = None
-    ctx.w_param, ctx.geom = weight.detach(), (stride, dilation)       # a detached alias: no flat-arena attributes (see conv2d_backward)
-    ctx.res_link, ctx.bn_src, ctx.x_half = None, None, None
-    dx, dw = ops.DwConv3x3Fn.backward(ctx, dy)[:2]
-    return dx, dw
+    state = ops.DwState(weight.detach(), (stride, dilation))       # a detached alias: no flat-arena attributes (see conv2d_backward)
+    return ops.dwconv3x3_backward(state, (ops.as_nhwc(x), None, None, None), (True, True), dy)
 
 
 @dwconv3x3_backward.register_fake
@@ -187,10 +150,10 @@ torch.library.register_autograd('pylc_hip::dwconv3x3', _dw_bwd, setup_context=_d
 @torch.library.custom_op('pylc_hip::batch_norm_act', mutates_args=())
 def batch_norm_act(y: Tensor, gamma: Tensor, beta: Tensor, running_mean: Tensor, running_var: Tensor, residual: Optional[Tensor],
                    relu: bool, training: bool, eps: float, momentum: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    ctx = _Ctx((False,) * 6)
     rm, rv = running_mean.clone(), running_var.clone()
-    out = ops.BnActFn.forward(ctx, y, gamma, beta, rm, rv, residual, relu, training, eps, momentum, None, False)
-    return out, ctx.saved_tensors[2], rm, rv
+    out, saved = ops._drive_collectives([ops.bn_act_forward((False,) * 6, y, gamma, beta, rm, rv, residual, relu, training, eps, momentum, None,
+                                                            False)], None)[0][:2]
+    return out, saved[2], rm, rv
 
 
 @batch_norm_act.register_fake
@@ -211,15 +174,12 @@ def bn_act_(y, gamma, beta, running_mean, running_var, residual=None, relu=False
 @torch.library.custom_op('pylc_hip::batch_norm_act_backward', mutates_args=())
 def batch_norm_act_backward(dout: Tensor, y: Tensor, out: Tensor, coef: Tensor, gamma: Tensor, has_residual: bool, relu: bool,
                             training: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    ctx = _Ctx((True, True, True, False, False, has_residual))
     b, c, h, w = y.shape
-    y = ops.as_nhwc(y)
-    ctx.save_for_backward(y, ops.as_nhwc(out) if (relu and has_residual) else None, coef, None, None, None)
-    ctx.cfg = (relu, training, None, float(b * h * w), has_residual)
-    ctx.g_param, ctx.b_param = gamma.detach(), gamma.detach()       # two detached aliases: no flat-arena attributes (see conv2d_backward)
-    ctx.want_amax, ctx.out_pl, ctx.drop, ctx.dy_pl, ctx.res_link, ctx.clamp = False, False, (0.0, 0), False, None, (False, 1e-5)
-    res = ops.BnActFn.backward(ctx, dout)
-    dy, dgamma, dbeta, dres = res[0], res[1], res[2], res[5]
+    # (two detached aliases of gamma: no flat-arena attributes, see conv2d_backward)
+    state = ops.BnState((relu, training, None, float(b * h * w), has_residual), gamma.detach(), gamma.detach())
+    saved = (ops.as_nhwc(y), ops.as_nhwc(out) if (relu and has_residual) else None, coef, None, None, None)
+    dy, dgamma, dbeta, _, _, dres = ops._drive_collectives([ops.bn_act_backward(state, saved, (True, True, True, False, False, has_residual),
+                                                                                dout)], None)[0]
     if dres is not None and dres.data_ptr() == dout.data_ptr():
         dres = dres.clone()          # an operator output may not alias an input
     return dy, dgamma, dbeta, _or_empty(dres, dout)
@@ -253,7 +213,7 @@ torch.library.register_autograd('pylc_hip::batch_norm_act', _bn_bwd, setup_conte
 # ------------------------------------------------------------------------------------------------------------------------------
 @torch.library.custom_op('pylc_hip::relu', mutates_args=())
 def relu(x: Tensor) -> Tensor:
-    return ops.ReluFn.forward(_Ctx((True,)), x)
+    return ops.relu_forward((True,), x)[0]
 
 
 @relu.register_fake
@@ -263,9 +223,7 @@ def _(x):
 
 @torch.library.custom_op('pylc_hip::relu_backward', mutates_args=())
 def relu_backward(dout: Tensor, out: Tensor) -> Tensor:
-    ctx = _Ctx((True,))
-    ctx.save_for_backward(ops.as_nhwc(out))
-    return ops.ReluFn.backward(ctx, dout)
+    return ops.relu_backward(None, (ops.as_nhwc(out),), (True,), dout)[0]
 
 
 @relu_backward.register_fake
@@ -279,9 +237,8 @@ torch.library.register_autograd('pylc_hip::relu', lambda ctx, d: torch.ops.pylc_
 
 @torch.library.custom_op('pylc_hip::max_pool2d', mutates_args=())
 def max_pool2d(x: Tensor, kernel: int, stride: int, padding: int) -> Tuple[Tensor, Tensor]:
-    ctx = _Ctx((True,))
-    y = ops.MaxPoolFn.forward(ctx, x, kernel, stride, padding, None)
-    return y, ctx.saved_tensors[0]
+    y, (idx,) = ops.maxpool_forward((True,), x, kernel, stride, padding)[:2]
+    return y, idx
 
 
 @max_pool2d.register_fake
@@ -293,11 +250,8 @@ def _(x, kernel, stride, padding):
 
 @torch.library.custom_op('pylc_hip::max_pool2d_backward', mutates_args=())
 def max_pool2d_backward(dy: Tensor, idx: Tensor, h: int, w: int, kernel: int, stride: int, padding: int) -> Tensor:
-    ctx = _Ctx((True,))
     b, c, oh, ow = dy.shape
-    ctx.save_for_backward(idx)
-    ctx.cfg, ctx.link = (b, c, h, w, kernel, stride, padding, oh, ow), None
-    return ops.MaxPoolFn.backward(ctx, dy)[0]
+    return ops.maxpool_backward(ops.PoolState((b, c, h, w, kernel, stride, padding, oh, ow)), (idx,), (True,), dy)[0]
 
 
 @max_pool2d_backward.register_fake
@@ -318,7 +272,7 @@ torch.library.register_autograd('pylc_hip::max_pool2d',
 
 @torch.library.custom_op('pylc_hip::bilinear', mutates_args=())
 def bilinear(x: Tensor, out_h: int, out_w: int) -> Tensor:
-    return ops.BilinearFn.forward(_Ctx((True,)), x, out_h, out_w)
+    return ops.bilinear_forward((True,), x, out_h, out_w)[0]
 
 
 @bilinear.register_fake
@@ -328,10 +282,7 @@ def _(x, out_h, out_w):
 
 @torch.library.custom_op('pylc_hip::bilinear_backward', mutates_args=())
 def bilinear_backward(dy: Tensor, h: int, w: int) -> Tensor:
-    ctx = _Ctx((True,))
-    b, c, oh, ow = dy.shape
-    ctx.cfg = (b, c, h, w, oh, ow)
-    return ops.BilinearFn.backward(ctx, dy)[0]
+    return ops.bilinear_backward(ops.ShapeState((dy.shape[0], dy.shape[1], h, w)), (), (True,), dy)[0]
 
 
 @bilinear_backward.register_fake
@@ -346,7 +297,7 @@ torch.library.register_autograd('pylc_hip::bilinear',
 
 @torch.library.custom_op('pylc_hip::global_avg_pool', mutates_args=())
 def global_avg_pool(x: Tensor) -> Tensor:
-    return ops.GapFn.forward(_Ctx((True,)), x)
+    return ops.gap_forward((True,), x)[0]
 
 
 @global_avg_pool.register_fake
@@ -356,10 +307,7 @@ def _(x):
 
 @torch.library.custom_op('pylc_hip::global_avg_pool_backward', mutates_args=())
 def global_avg_pool_backward(dy: Tensor, h: int, w: int) -> Tensor:
-    ctx = _Ctx((True,))
-    ctx.cfg = (dy.shape[0], dy.shape[1], h, w)
-    ctx.res_link = None
-    return ops.GapFn.backward(ctx, dy)[0]
+    return ops.gap_backward(ops.ShapeState((dy.shape[0], dy.shape[1], h, w)), (), (True,), dy)[0]
 
 
 @global_avg_pool_backward.register_fake
@@ -374,7 +322,7 @@ torch.library.register_autograd('pylc_hip::global_avg_pool',
 
 @torch.library.custom_op('pylc_hip::dropout', mutates_args=())
 def dropout(x: Tensor, p: float, seed: int) -> Tensor:
-    return ops.DropoutFn.forward(_Ctx((True,)), x, p, seed)
+    return ops.dropout_forward((True,), x, p, seed)[0]
 
 
 @dropout.register_fake
@@ -392,9 +340,8 @@ torch.library.register_autograd('pylc_hip::dropout',
 # ------------------------------------------------------------------------------------------------------------------------------
 @torch.library.custom_op('pylc_hip::multiloss', mutates_args=())
 def multiloss(logits: Tensor, target: Tensor, class_weights: Optional[Tensor], w_ce: float, w_dice: float, w_focal: float) -> Tuple[Tensor, Tensor]:
-    ctx = _Ctx((True,))
-    losses = ops.MultiLossFn.forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, None)
-    return losses, ctx.saved_tensors[2]
+    losses, saved = ops.multiloss_forward((True,), logits, target, class_weights, w_ce, w_dice, w_focal, None)[:2]
+    return losses, saved[2]
 
 
 @multiloss.register_fake
@@ -405,11 +352,9 @@ def _(logits, target, class_weights, w_ce, w_dice, w_focal):
 @torch.library.custom_op('pylc_hip::multiloss_backward', mutates_args=())
 def multiloss_backward(dlosses: Tensor, logits: Tensor, target: Tensor, stats: Tensor, class_weights: Optional[Tensor], w_ce: float,
                        w_dice: float, w_focal: float) -> Tensor:
-    ctx = _Ctx((True,))
     b, c, h, w = logits.shape
-    ctx.save_for_backward(ops.as_nhwc(logits), target.contiguous(), stats, class_weights)
-    ctx.cfg = (float(b * h * w), w_ce, w_dice, w_focal, None)
-    return ops.MultiLossFn.backward(ctx, dlosses)[0]
+    return ops.multiloss_backward(ops.LossState((float(b * h * w), w_ce, w_dice, w_focal, None)),
+                                  (ops.as_nhwc(logits), target.contiguous(), stats, class_weights), (True,), dlosses)[0]
 
 
 @multiloss_backward.register_fake
@@ -437,10 +382,9 @@ torch.library.register_autograd('pylc_hip::multiloss', _ml_bwd, setup_context=_m
 @torch.library.custom_op('pylc_hip::multiloss_ignore', mutates_args=())
 def multiloss_ignore(logits: Tensor, target: Tensor, class_weights: Optional[Tensor], w_ce: float, w_dice: float, w_focal: float,
                      ignore_index: int) -> Tuple[Tensor, Tensor, Tensor]:
-    ctx = _Ctx((True,))
     bad = torch.zeros(1, dtype=torch.int64, device=logits.device)
-    losses = ops.MultiLossFn.forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, None, ignore_index, bad)
-    return losses, ctx.saved_tensors[2], bad
+    losses, saved = ops.multiloss_forward((True,), logits, target, class_weights, w_ce, w_dice, w_focal, None, ignore_index, bad)[:2]
+    return losses, saved[2], bad
 
 
 @multiloss_ignore.register_fake
@@ -451,11 +395,8 @@ def _(logits, target, class_weights, w_ce, w_dice, w_focal, ignore_index):
 @torch.library.custom_op('pylc_hip::multiloss_ignore_backward', mutates_args=())
 def multiloss_ignore_backward(dlosses: Tensor, logits: Tensor, target: Tensor, stats: Tensor, class_weights: Optional[Tensor], w_ce: float,
                               w_dice: float, w_focal: float, ignore_index: int) -> Tensor:
-    ctx = _Ctx((True,))
-    ctx.save_for_backward(ops.as_nhwc(logits), target.contiguous(), stats, class_weights)
-    ctx.cfg = (None, w_ce, w_dice, w_focal, None)
-    ctx.ignore = ignore_index
-    return ops.MultiLossFn.backward(ctx, dlosses)[0]
+    return ops.multiloss_backward(ops.LossState((None, w_ce, w_dice, w_focal, None), ignore_index),
+                                  (ops.as_nhwc(logits), target.contiguous(), stats, class_weights), (True,), dlosses)[0]
 
 
 @multiloss_ignore_backward.register_fake
@@ -483,10 +424,9 @@ torch.library.register_autograd('pylc_hip::multiloss_ignore', _mli_bwd, setup_co
 @torch.library.custom_op('pylc_hip::multiloss_weighted', mutates_args=())
 def multiloss_weighted(logits: Tensor, target: Tensor, pixel_weights: Tensor, class_weights: Optional[Tensor], w_ce: float, w_dice: float,
                        w_focal: float, ignore_index: Optional[int]) -> Tuple[Tensor, Tensor, Tensor]:
-    ctx = _Ctx((True,))
     bad = torch.zeros(1, dtype=torch.int64, device=logits.device)
-    losses = ops.MultiLossFn.forward(ctx, logits, target, class_weights, w_ce, w_dice, w_focal, None, ignore_index, bad, pixel_weights)
-    return losses, ctx.saved_tensors[2], bad
+    losses, saved = ops.multiloss_forward((True,), logits, target, class_weights, w_ce, w_dice, w_focal, None, ignore_index, bad, pixel_weights)[:2]
+    return losses, saved[2], bad
 
 
 @multiloss_weighted.register_fake
@@ -498,11 +438,9 @@ def _(logits, target, pixel_weights, class_weights, w_ce, w_dice, w_focal, ignor
 def multiloss_weighted_backward(dlosses: Tensor, logits: Tensor, target: Tensor, pixel_weights: Tensor, stats: Tensor,
                                 class_weights: Optional[Tensor], w_ce: float, w_dice: float, w_focal: float,
                                 ignore_index: Optional[int]) -> Tensor:
-    ctx = _Ctx((True,))
-    ctx.save_for_backward(ops.as_nhwc(logits), target.contiguous(), stats, class_weights, pixel_weights.contiguous())
-    ctx.cfg = (None, w_ce, w_dice, w_focal, None)
-    ctx.ignore = ops.MultiLossFn.NO_IGNORE if ignore_index is None else ignore_index
-    return ops.MultiLossFn.backward(ctx, dlosses)[0]
+    state = ops.LossState((None, w_ce, w_dice, w_focal, None), ops.MultiLossFn.NO_IGNORE if ignore_index is None else ignore_index)
+    return ops.multiloss_backward(state, (ops.as_nhwc(logits), target.contiguous(), stats, class_weights, pixel_weights.contiguous()), (True,),
+                                  dlosses)[0]
 
 
 @multiloss_weighted_backward.register_fake

@@ -56,6 +56,31 @@ def test_custom_ops_match_the_ops_path(dev):
     assert torch.equal(o0, o1) and torch.equal(rm0, rm1) and torch.equal(rv0, rv1)
     for a, c in zip(gb0, (yb.grad, ga.grad, be.grad, res.grad)):
         assert torch.equal(a, c)
+    # thin-input stem: the 3-channel 7x7 / stride-2 filter on the 4-channel input pack (the operator's backward pads the filter itself)
+    xs = nhwc(rnd(13, 2, 4, 20, 24), dev).requires_grad_(True)
+    ws = nhwc(rnd(14, 64, 3, 7, 7, scale=0.05), dev).requires_grad_(True)
+    dys = nhwc(rnd(15, 2, 64, 10, 12), dev)
+    got = []
+    for f in (ops.conv2d, P.conv2d):
+        ys = f(xs, ws, None, 2, 3, 1)
+        ys.backward(dys)
+        ops.sync_side_streams()
+        got.append((ys, xs.grad.clone(), ws.grad.clone()))
+        xs.grad = ws.grad = None
+    for a, c in zip(*got):
+        assert a.shape == c.shape and torch.equal(a, c)
+    # BatchNorm in eval mode (running statistics) with and without residual, and in training mode without ReLU or residual
+    yb.grad = ga.grad = be.grad = res.grad = None
+    for residual, relu_, training in ((res, True, False), (None, True, False), (None, False, True)):
+        got = []
+        for f in (ops.bn_act, bn_act_):
+            rm, rv = (0.1 * rnd(16, 96)).to(dev), (1 + 0.1 * rnd(17, 96).abs()).to(dev)
+            o = f(yb, ga, be, rm, rv, residual, relu_, training)
+            o.backward(dy)
+            got.append((o, rm, rv, yb.grad.clone(), ga.grad.clone(), be.grad.clone()) + ((res.grad.clone(),) if residual is not None else ()))
+            yb.grad = ga.grad = be.grad = res.grad = None
+        for i, (a, c) in enumerate(zip(*got)):
+            assert torch.equal(a, c), (relu_, training, i)
     # pooling / resize / activation / dropout
     t = nhwc(rnd(9, 2, 64, 17, 19), dev).requires_grad_(True)
     for f0, f1 in ((lambda v: ops.maxpool(v, 3, 2, 1), lambda v: P.max_pool2d(v, 3, 2, 1)[0]),
