@@ -696,6 +696,11 @@ int pylc_blend_accumulate(const float* logits, int pitch, int first_tile, int n_
  * value (the same float as probs[mask]). */
 int pylc_blend_finalize(const float* acc, int acc_pitch, int H, int W, int out, int stride, int C, int members,
                         unsigned char* mask, float* probs, float* conf, void* stream);
+/* pylc_blend_accumulate with a trailing inverse temperature (> 0, finite; PYLC_ERR_ARG otherwise): the tile's term is
+ * softmax(inv_temperature * logits), the exponent taken as (z_c - z_max) * inv_temperature in fp32.  A separate instantiation of
+ * the kernel: inv_temperature == 1.0f gives pylc_blend_accumulate's bytes. */
+int pylc_blend_accumulate_t(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
+                            int flip, float* acc, int acc_pitch, void* stream, float inv_temperature);
 /* pylc_image_pack_tiles_ex with a trailing flip: flip = 1 writes every window mirrored along x (output column c0 reads source
  * column x0 + tile - 1 - c0); flip = 0 gives pylc_image_pack_tiles_ex's bytes.  Its own checks, then the shared cutter
  * (csrc/pack_tiles.hip). */
@@ -797,6 +802,46 @@ int pylc_logits_score(const float* logits, int pitch, const void* target, int ta
  * is allowed) adds to counts[C*C + 1], any other target outside 0..C-1 to counts[C*C], and neither enters the matrix. */
 int pylc_logits_score_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, unsigned char* mask,
                          int ignore_index, unsigned long long* counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Calibration of confidences (csrc/calibration.hip; not in the reference): reliability counts, from which the
+ * expected / maximum calibration error follow on the host, and the negative log-likelihood on a grid of inverse temperatures,
+ * from which one temperature is fitted.  C in 2..PYLC_MAX_CLASSES, 1 <= N <= 2^39, bins B in 1..32.  Every entry point checks its
+ * arguments on the host (PYLC_ERR_ARG, nothing is launched), allocates nothing and enqueues on `stream`; targets are uint8
+ * (*_bytes = 1) or int64 (8) class indices.  Definitions:
+ *   bin of a float32 confidence p:   min(B - 1, (int)(p * (float)B)) -- fp32 product, truncating conversion; p == 1 is in the last bin
+ *   quantised confidence:            q = (uint32)(p * 16777216.0f) -- the product is exact, the conversion truncates
+ *   counts: int64 [3*C*B + 3], zeroed by the caller and ADDED into with integer atomics (exact, independent of pixel order).
+ *     For predicted class c and bin b the entries (c*B + b)*3 + {0, 1, 2} are the number of pixels, the number of those whose
+ *     target is c, and the sum of q.  The tail 3*C*B + {0, 1, 2} counts targets outside 0..C-1 that are not the ignore label
+ *     (for pylc_reliability_counts also predicted classes outside 0..C-1), targets equal to the ignore label (has_ignore = 1;
+ *     compared after widening, an index inside 0..C-1 is allowed), and confidences that are NaN, infinite or outside [0, 1].  A
+ *     tail pixel is counted in its tail cell only: in the ignore cell if its target is the ignore label, else the first of the others.
+ *   One `counts` may take launches over fewer than 2^39 pixels in all (the int64 bound of a q sum).
+ * ------------------------------------------------------------------------------------------- */
+/* conf: float32 [N] (4-B aligned), pred: uint8 [N], truth: uint8 / int64 [N] -- the maps pylc_blend_finalize and
+ * pylc_class_encode_resize leave on the device.  Read with one 16-byte / 4-byte load per group of four pixels when conf is
+ * 16-byte and the byte masks are 4-byte aligned, pixel by pixel otherwise. */
+int pylc_reliability_counts(const float* conf, const unsigned char* pred, const void* truth, int truth_bytes, long long N, int C, int B,
+                            int has_ignore, int ignore_index, unsigned long long* counts, void* stream);
+/* From NHWC logits (N rows of `pitch` >= C floats, 16-byte loads when pitch % 4 == 0 and the base is 16-byte aligned): the class
+ * is the FIRST maximum (strict `>`), conf = 1 / sum_c expf((z_c - z_max) * inv_temperature) in fp32, the sum taken in ascending
+ * c; inv_temperature > 0 and finite.  mask_out: NULL or uint8 [N], any alignment; conf_out: NULL or float32 [N], the very float
+ * that was binned; counts: NULL (maps only; then target may be NULL with target_bytes 0) or as above.  All three NULL, counts
+ * without target: PYLC_ERR_ARG. */
+int pylc_logits_reliability(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int B,
+                            float inv_temperature, int has_ignore, int ignore_index, unsigned char* mask_out, float* conf_out,
+                            unsigned long long* counts, void* stream);
+/* betas: K in 1..32 positive finite floats ON THE HOST (passed to the kernel by value).  For every k,
+ * sums[k] += sum over the pixels whose target is a class (and not the ignore label) of
+ *   logf(sum_c expf((z_c - z_max) * betas[k])) - (z_t - z_max) * betas[k]      (fp32 per pixel, ascending c)
+ * accumulated in fp64: per thread, then by a fixed tree per block into `workspace`, then over the blocks in block order.  The
+ * number of blocks depends on N alone and no float atomics are used, so the result is bitwise reproducible.  tail: int64 [3],
+ * ADDED into: pixels summed, out-of-range targets, ignored targets.  workspace: pylc_logits_nll_grid_workspace_bytes(N, K)
+ * bytes, 8-B aligned, private to the launch until it has finished (0 for N or K out of range). */
+size_t pylc_logits_nll_grid_workspace_bytes(long long N, int K);
+int pylc_logits_nll_grid(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, const float* betas,
+                         int K, int has_ignore, int ignore_index, void* workspace, double* sums, long long* tail, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Connected regions of a class mask and the small-region sieve (csrc/regions.hip; not in the reference).

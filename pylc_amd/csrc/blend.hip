@@ -25,9 +25,10 @@ namespace {
 // the pixels [y0, y0 + bh) x [x0, x0 + bw) that the tiles first .. first + count - 1 can touch
 struct BlendBox { int y0, x0, bh, bw; };
 
-template <int C>
+// TEMP: the tile's term is softmax(beta * logits) (pylc_blend_accumulate_t); without it `beta` is not read
+template <int C, bool TEMP>
 __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __restrict__ logits, BlendGeom g, BlendBox box, int first, int count,
-                                                                int flip, float* __restrict__ acc) {
+                                                                int flip, float* __restrict__ acc, float beta) {
     constexpr int NV = (C + 3) / 4;
     const long long total = (long long)box.bh * box.bw;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -56,7 +57,8 @@ __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __re
                 int lx = x - overlap_origin(tj, g.W, g.out, g.stride);
                 lx = flip ? g.out - 1 - lx : lx;
                 const ot_f32x4* src = reinterpret_cast<const ot_f32x4*>(logits + (((size_t)k * g.out + ly) * g.out + lx) * g.pitch);
-                softmax_add<C>(src, a);              // stitch_overlap_kernel's term, operation for operation
+                if constexpr (TEMP) softmax_add<C, NV * 4, true>(src, a, beta);
+                else softmax_add<C>(src, a);         // stitch_overlap_kernel's term, operation for operation
             }
         }
         if (loaded) {                     // a pixel of the box that no tile of the batch covers is not written
@@ -75,8 +77,9 @@ __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __re
 
 using namespace pylc;
 
-extern "C" int pylc_blend_accumulate(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
-                                     int flip, float* acc, int acc_pitch, void* stream) {
+template <bool TEMP>
+static int blend_accumulate_impl(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
+                                 int flip, float* acc, int acc_pitch, void* stream, float beta) {
     PYLC_REQUIRE(logits && pitch >= C && pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0,
                  "blend_accumulate: logits must be 16-B aligned NHWC tiles with a pitch >= C, multiple of 4");
     PYLC_REQUIRE(acc && acc_pitch >= C && acc_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(acc) & 15) == 0,
@@ -102,11 +105,22 @@ extern "C" int pylc_blend_accumulate(const float* logits, int pitch, int first_t
     const BlendGeom g{H, W, out, stride, rows, cols, pitch, acc_pitch};
     const int blocks = ot_grid((long long)box.bh * box.bw);
     hipStream_t st = as_stream(stream);
-#define LAUNCH_BA(CC) hipLaunchKernelGGL((blend_accumulate_kernel<CC>), dim3(blocks), dim3(256), 0, st, logits, g, box, first_tile, n_tiles, flip, acc)
+#define LAUNCH_BA(CC) hipLaunchKernelGGL((blend_accumulate_kernel<CC, TEMP>), dim3(blocks), dim3(256), 0, st, logits, g, box, first_tile, n_tiles, flip, acc, beta)
     PYLC_FOR_CLASSES(C, LAUNCH_BA, "blend_accumulate")
 #undef LAUNCH_BA
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
+}
+
+extern "C" int pylc_blend_accumulate(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
+                                     int flip, float* acc, int acc_pitch, void* stream) {
+    return blend_accumulate_impl<false>(logits, pitch, first_tile, n_tiles, H, W, out, stride, C, flip, acc, acc_pitch, stream, 1.f);
+}
+
+extern "C" int pylc_blend_accumulate_t(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
+                                       int flip, float* acc, int acc_pitch, void* stream, float inv_temperature) {
+    PYLC_REQUIRE(inv_temperature > 0.f && inv_temperature <= 3.4028234e38f, "blend_accumulate_t: inv_temperature must be positive and finite");
+    return blend_accumulate_impl<true>(logits, pitch, first_tile, n_tiles, H, W, out, stride, C, flip, acc, acc_pitch, stream, inv_temperature);
 }
 
 extern "C" int pylc_blend_finalize(const float* acc, int acc_pitch, int H, int W, int out, int stride, int C, int members, unsigned char* mask,

@@ -35,8 +35,10 @@ __device__ __forceinline__ Cover overlap_cover(int y, int n, int out, int stride
 
 // acc[c] += softmax(v)[c] for the C logits that start at the 16-byte aligned `src` (pitch >= C rounded up to 4): the per-tile term of the
 // mean-probability blend, stated once so that the one-shot and the streaming blend add the same bits in the same order.
-template <int C, int N>
-__device__ __forceinline__ void softmax_add(const ot_f32x4* __restrict__ src, float (&acc)[N]) {
+// TEMP (pylc_blend_accumulate_t): softmax(beta * v), the exponent taken as (v - max) * beta -- beta = 1 multiplies by
+// 1.0f, which is exact, and gives the bytes of the plain form; without TEMP `beta` is not read and the code is the plain form's.
+template <int C, int N, bool TEMP = false>
+__device__ __forceinline__ void softmax_add(const ot_f32x4* __restrict__ src, float (&acc)[N], float beta = 1.f) {
     constexpr int NV = (C + 3) / 4;
     float v[NV * 4];
 #pragma unroll
@@ -49,7 +51,11 @@ __device__ __forceinline__ void softmax_add(const ot_f32x4* __restrict__ src, fl
     for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
     float s = 0.f;
 #pragma unroll
-    for (int c = 0; c < C; ++c) { v[c] = expf(v[c] - m); s += v[c]; }
+    for (int c = 0; c < C; ++c) {
+        if constexpr (TEMP) v[c] = expf((v[c] - m) * beta);
+        else v[c] = expf(v[c] - m);
+        s += v[c];
+    }
     const float inv = 1.f / s;
 #pragma unroll
     for (int c = 0; c < C; ++c) acc[c] += v[c] * inv;

@@ -114,7 +114,7 @@ def _eval_mode(model):
 
 
 def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blend='reference', flip=False, return_probs=False,
-                  return_confidence=False, scales=None, scale_weights=None):
+                  return_confidence=False, scales=None, scale_weights=None, temperature=None):
     """image: [C,H,W] raw 0..255, uint8 or float (host or device), fitted.  Returns the uint8 class mask [H,W] (device).
 
     group=None (default): LOCAL -- this process runs every tile and returns the mask, also inside a data-parallel job (a rank-0-only
@@ -128,18 +128,22 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blen
     mask, or the tuple (mask[, probs][, conf]) in that order -- probs fp32 [n_classes,H,W], conf fp32 [H,W] its maximum over the classes.
     flip=True adds the horizontally mirrored windows as a second ensemble member.  scales=(0.75, 1.0, 1.25) runs the multi-scale ensemble
     (predict_blend_mean: the image at every scale, the probabilities resampled back and averaged with scale_weights); like flip it needs
-    blend='mean'.
+    blend='mean'.  temperature (resolve_temperature: None, a positive float, or 'meta' for model.meta.temperature) divides the logits
+    before every tile's softmax (pylc_blend_accumulate_t); like flip it needs blend='mean' and composes with flip and scales.
 
     A U-Net model (meta.arch == 'unet') takes predict_overlap_tile instead (any image size, stride default tile - 2*pad); its blend
     always was the mean, so `blend` is ignored and the other keywords pass through."""
     if blend not in ('reference', 'mean'):
         raise ValueError("blend is 'reference' or 'mean', got %r" % (blend,))
     if model.meta.arch == 'unet':
-        return predict_overlap_tile(model, image, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights)
+        return predict_overlap_tile(model, image, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights,
+                                    temperature)
     if blend == 'mean':
-        return predict_blend_mean(model, image, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights)
+        return predict_blend_mean(model, image, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights,
+                                  temperature)
     asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence),
-                            ('scales', scales is not None), ('scale_weights', scale_weights is not None)) if v]
+                            ('scales', scales is not None), ('scale_weights', scale_weights is not None),
+                            ('temperature', temperature is not None)) if v]
     if asked:
         raise ValueError("%s needs blend='mean': the reference stitch mixes logits and probabilities, its scores are not probabilities"
                          % ', '.join(asked))
@@ -210,7 +214,7 @@ def overlap_tile_out(net, tile, pad):
 
 
 def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=None, return_probs=False, flip=False, return_confidence=False,
-                         scales=None, scale_weights=None):
+                         scales=None, scale_weights=None, temperature=None):
     """Full-image U-Net inference by overlap tiles.  image: [C,H,W] raw 0..255, uint8 or float, host or device, any H, W >= out
     (out = tile - 2*meta.pad_size; no fitting).  stride in [1, out], default out.  Returns the uint8 class mask [H,W] (device), or
     (mask, probs) with probs the fp32 mean softmax probabilities [n_classes,H,W] when return_probs.
@@ -222,14 +226,15 @@ def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=Non
 
     flip=True (the mirrored windows as a second ensemble member), return_confidence=True (the tuple grows by conf, fp32 [H,W], the
     maximum probability) or scales (the multi-scale ensemble) move the call to the streaming accumulator, predict_blend_mean; without
-    them it is the one-launch stitch."""
+    them it is the one-launch stitch.  So does temperature (predict_image's keyword)."""
     if model.meta.arch != 'unet':
         raise ValueError('predict_overlap_tile needs a U-Net (meta.arch == "unet"), got %r' % model.meta.arch)
     L.init()
     pad = model.meta.pad_size
     out = overlap_tile_out(model.net, tile, pad)
-    if flip or return_confidence or scales is not None or scale_weights is not None:
-        return predict_blend_mean(model, image, tile, out, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights)
+    if flip or return_confidence or scales is not None or scale_weights is not None or temperature is not None:
+        return predict_blend_mean(model, image, tile, out, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights,
+                                  temperature)
     stride = out if stride is None else int(stride)
     run = _TileRun(model, image, group)
     row_o, col_o = overlap_tile_grid(run.h, run.w, out, stride, pad)
@@ -298,9 +303,27 @@ def ensemble_plan(scales, scale_weights, h, w, out):
     return plan
 
 
-def _blend_sweep(run, img, tile, out, stride, batch, members):
+def resolve_temperature(model, temperature):
+    """The inference keyword `temperature` as an inverse temperature: None stays None (the plain entry point), a positive finite number T
+    gives 1 / T, 'meta' takes model.meta.temperature and raises ValueError when no validation pass has stored one."""
+    if temperature is None:
+        return None
+    if isinstance(temperature, str):
+        if temperature != 'meta':
+            raise ValueError("temperature is None, a positive number or 'meta', got %r" % (temperature,))
+        temperature = getattr(model.meta, 'temperature', None)
+        if temperature is None:
+            raise ValueError("temperature='meta', but model.meta.temperature is unset: train with calibration_bins, or pass a number")
+    t = float(temperature)
+    if not (t > 0.0 and t != float('inf')):
+        raise ValueError('temperature must be a positive finite number, got %r' % (temperature,))
+    return 1.0 / t
+
+
+def _blend_sweep(run, img, tile, out, stride, batch, members, beta=None):
     """predict_blend_mean's sweep over one device image [C,H,W] (uint8 or float32; run.img or another size of it): this rank's share of
-    the tile batches, member-major, into a zeroed accumulation image [H,W,cp], which it returns.  The network is in eval mode already."""
+    the tile batches, member-major, into a zeroed accumulation image [H,W,cp], which it returns.  The network is in eval mode already.
+    beta: None, or the inverse temperature of pylc_blend_accumulate_t."""
     h, w = img.shape[1:]
     row_o, col_o = overlap_tile_grid(h, w, out, stride, (tile - out) // 2)
     mine = run.mine(len(row_o) * len(col_o), batch)
@@ -316,12 +339,15 @@ def _blend_sweep(run, img, tile, out, stride, batch, members):
                 y2 = ops.zeros_nhwc(b, ncls, out, out, run.dev, pitch=cp)
                 y2.copy_(y)
                 y, p = y2, cp
-            check(lib.pylc_blend_accumulate(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream()))
+            if beta is None:
+                check(lib.pylc_blend_accumulate(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream()))
+            else:
+                check(lib.pylc_blend_accumulate_t(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream(), beta))
     return acc
 
 
 def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None, flip=False, return_probs=False, return_confidence=False,
-                       scales=None, scale_weights=None):
+                       scales=None, scale_weights=None, temperature=None):
     """The streaming mean-probability blend (csrc/blend.hip) for a network that maps a `tile` window to its centred `out`
     square (DeepLab: out = tile; U-Net: out = tile - 2*pad).  image: [C,H,W] raw 0..255, uint8 or float, any H, W >= out; stride in
     [1, out], default tile // 2 for a same-size network and out otherwise.
@@ -346,7 +372,10 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
     process's by fp32 summation order only; a one-rank group equals no group bit for bit), rank 0 finalizes, the others return None.
     With scales every rank resamples its own partial sums into its own ensemble image -- the divisor of a pixel is a constant of the
     geometry, so the step is linear -- and one all_reduce of the ensemble image runs at the end.
+    temperature: None, a positive number T or 'meta' (resolve_temperature); with one, every tile's term is softmax(logits / T) through
+    pylc_blend_accumulate_t, at every member and scale.  T = 1 gives the bytes of None.
     Returns mask, or (mask[, probs][, conf])."""
+    beta = resolve_temperature(model, temperature)                     # before any launch
     if stride is None:
         stride = tile // 2 if out == tile else out
     stride = int(stride)
@@ -361,11 +390,11 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
     acc = ens = None
     with _eval_mode(model):
         if plan is None:
-            acc = _blend_sweep(run, img, tile, out, stride, batch, members)
+            acc = _blend_sweep(run, img, tile, out, stride, batch, members, beta)
         else:
             ens = torch.empty((h, w, cp), device=run.dev)             # the first scale's launch writes every channel below ncls
             for k, (_, hs, ws, wgt) in enumerate(plan):
-                acc_s = _blend_sweep(run, img if (hs, ws) == (h, w) else resize_image(img, hs, ws), tile, out, stride, batch, members)
+                acc_s = _blend_sweep(run, img if (hs, ws) == (h, w) else resize_image(img, hs, ws), tile, out, stride, batch, members, beta)
                 check(lib.pylc_blend_resample_accumulate(ptr(acc_s), cp, hs, ws, out, stride, members, wgt, ncls, ptr(ens), cp, h, w,
                                                          int(k > 0), stream()))
                 del acc_s

@@ -201,6 +201,7 @@ SIGNATURES = {
     'pylc_image_pack_tiles_flip': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P, _I]),
     'pylc_image_pack_tiles_reflect_ex': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P, _I]),
     'pylc_blend_accumulate': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    'pylc_blend_accumulate_t': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _F]),
     'pylc_blend_finalize': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     'pylc_resize_bilinear_image': (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
     'pylc_blend_resample_accumulate': (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _I, _I, _I, _I, _P]),
@@ -214,6 +215,10 @@ SIGNATURES = {
     'pylc_confusion_matrix_ex': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _I, _P, _P]),
     'pylc_logits_score': (_I, [_P, _I, _P, _I, _LL, _I, _P, _P, _P]),
     'pylc_logits_score_ex': (_I, [_P, _I, _P, _I, _LL, _I, _P, _I, _P, _P]),
+    'pylc_reliability_counts': (_I, [_P, _P, _P, _I, _LL, _I, _I, _I, _I, _P, _P]),
+    'pylc_logits_reliability': (_I, [_P, _I, _P, _I, _LL, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
+    'pylc_logits_nll_grid_workspace_bytes': (_SZ, [_LL, _I]),
+    'pylc_logits_nll_grid': (_I, [_P, _I, _P, _I, _LL, _I, C.POINTER(_F), _I, _I, _I, _P, _P, _P, _P]),
     'pylc_label_regions': (_I, [_P, _I, _I, _I, _I, _P, _P]),
     'pylc_region_sizes': (_I, [_P, _LL, _P, _P]),
     'pylc_sieve_regions': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -108,7 +108,7 @@ class ScoreLog:
     """Validation scores next to the loss log: add() accumulates the confusion counts of every validation batch on the device (one launch,
     no host read), close() turns them into one row per validation pass -- the only D2H copy -- and tracks the best weighted IoU."""
 
-    def __init__(self, n_classes, ignore_index=None, boundary_radius=None):
+    def __init__(self, n_classes, ignore_index=None, boundary_radius=None, calibration_bins=None):
         self.n_classes = int(n_classes)
         self.ignore_index = None if ignore_index is None else int(ignore_index)      # targets equal to it are dropped and reported as 'ignored'
         # with a radius, add() also counts the band along class borders (boundary.boundary_counts on the mask of the same launch) and the
@@ -120,6 +120,15 @@ class ScoreLog:
             boundary._check_classes(self.n_classes)
             boundary._check_ignore(self.ignore_index)
         self.boundary_counts = None        # int64 [C*C + 3C + 1], allocated with `counts`
+        # with bins, add() also takes the batch's reliability counts at temperature 1 (one launch) and its NLL on calibration.default_betas()
+        # (33 betas: two launches), and the rows gain 'ece', 'mce', 'nll', 'class_ece' and the pass's fitted 'temperature' (DESIGN.md 5.20);
+        # without, nothing changes
+        self.calibration_bins = None
+        self.reliability_counts = None     # int64 [3*C*bins + 3]
+        self.nll_sums = None               # float64 [len(betas)]
+        self.nll_tail = None               # int64 [3]
+        if calibration_bins is not None:
+            self.set_calibration(calibration_bins)
         self.counts = None                 # int64 [C*C + 1] (+ 1 with an ignore label), allocated where the first logits live
         self.last_counts = None            # host int64 [C,C] of the last closed pass (summed over the group)
         self.rows = []
@@ -128,11 +137,30 @@ class ScoreLog:
     def _zeros(self, device):
         return torch.zeros(self.n_classes * self.n_classes + (1 if self.ignore_index is None else 2), device=device, dtype=torch.int64)
 
+    def set_calibration(self, bins):
+        """Switch the calibration rows on for the passes to come (a log taken up from a checkpoint starts without them)."""
+        from . import calibration
+        self.calibration_bins = calibration._check_bins(bins)
+        self.betas = calibration.default_betas()
+        self.reliability_counts = self.nll_sums = self.nll_tail = None
+
+    def _calibration_zeros(self, device):
+        from . import calibration
+        self.reliability_counts = torch.zeros(calibration.n_cells(self.n_classes, self.calibration_bins), device=device, dtype=torch.int64)
+        self.nll_sums = torch.zeros(len(self.betas), device=device, dtype=torch.float64)
+        self.nll_tail = torch.zeros(3, device=device, dtype=torch.int64)
+
     def add(self, logits, target):
         if logits.shape[1] != self.n_classes:
             raise ValueError('ScoreLog of %d classes got logits with %d' % (self.n_classes, logits.shape[1]))
         if self.counts is None:
             self.counts = self._zeros(logits.device)
+        if self.calibration_bins is not None:
+            from . import calibration
+            if self.reliability_counts is None:
+                self._calibration_zeros(logits.device)
+            calibration.logits_reliability(logits, target, self.calibration_bins, counts=self.reliability_counts, ignore_index=self.ignore_index)
+            calibration.nll_grid(logits, target, self.betas, self.ignore_index, sums=self.nll_sums, tail=self.nll_tail)
         if self.boundary_radius is None:
             logits_confusion(logits, target, counts=self.counts, ignore_index=self.ignore_index)
             return
@@ -148,7 +176,9 @@ class ScoreLog:
         """End of a validation pass: the counts (summed over `group` when given -- a collective every rank must reach) become a row
         {'iter', 'epoch', 'f1', 'iou', 'mcc', 'class_iou', 'class_f1', 'support'} (with an ignore label also 'ignored', the number of
         dropped pixels; with a boundary radius also 'boundary_iou', 'trimap_iou', 'class_boundary_iou'); the device counts are zeroed
-        for the next pass.  Returns the row, or None when no valid pixel was added."""
+        for the next pass.  With calibration bins the row also has 'ece', 'mce', 'class_ece', 'nll' (the mean negative log-likelihood at
+        temperature 1) and 'temperature' (calibration.fit_temperature of this pass; the grid's end when the minimum lies outside it).
+        Returns the row, or None when no valid pixel was added."""
         c = self.n_classes
         if self.counts is None:
             self.counts = self._zeros('cpu')           # a rank that saw no batch still takes part in the collective
@@ -164,6 +194,16 @@ class ScoreLog:
                 runtime.sync_all_reduce(self.boundary_counts, group)
             bhost = self.boundary_counts.to('cpu', copy=True)
             self.boundary_counts.zero_()
+        rhost = None
+        if self.calibration_bins is not None:
+            if self.reliability_counts is None:
+                self._calibration_zeros(self.counts.device)
+            if group is not None:                                   # int64 and fp64: carried by the torch group, as the confusion counts
+                for t in (self.reliability_counts, self.nll_sums, self.nll_tail):
+                    runtime.sync_all_reduce(t, group)
+            rhost = [t.to('cpu', copy=True) for t in (self.reliability_counts, self.nll_sums, self.nll_tail)]
+            for t in (self.reliability_counts, self.nll_sums, self.nll_tail):
+                t.zero_()
         host = self.counts.to('cpu', copy=True)                    # the one D2H copy of a validation pass (two with a boundary radius)
         self.counts.zero_()
         outside = int(host[c * c])
@@ -182,6 +222,12 @@ class ScoreLog:
         if bhost is not None:
             b = boundary.boundary_scores(bhost, c)
             row.update(boundary_iou=b['boundary_iou'], trimap_iou=b['trimap_iou'], class_boundary_iou=[float(v) for v in b['class_boundary_iou']])
+        if rhost is not None:
+            from . import calibration
+            r = calibration.reliability_scores(rhost[0], c, self.calibration_bins)
+            fit = calibration.fit_temperature(self.betas, rhost[1], int(rhost[2][0]))
+            row.update(ece=r['ece'], mce=r['mce'], class_ece=[float(v) for v in r['class_ece']], nll=fit['nll_at_1'],
+                       temperature=fit['temperature'])
         self.rows.append(row)
         self.is_best = row['iou'] > self.best_iou
         if self.is_best:

@@ -55,6 +55,8 @@ class Meta:
         self.ignore_index = None           # an int (255 for uint8 masks): pixels with this label are left out of the loss and the scores
         self.border_weight = None          # None, or {'w0':, 'sigma':, 'radius':}: training weighs a pixel by 1 + w0 exp(-d^2 / (2 sigma^2)) of its
         #                                    distance d to the nearest pixel of another class within `radius` (boundary.border_profile)
+        self.temperature = None            # None, or the temperature fitted on the last validation pass (trainer(calibration_bins=...), DESIGN.md
+        #                                    5.20): what the inference keyword temperature='meta' divides the logits by
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise AttributeError('unknown Meta field %r' % k)

@@ -188,7 +188,7 @@ def _sieve_result(res, pal, min_region, connectivity, fill, ignore_index):
 
 def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None, batch=8, group=None, return_probs=False, blend='reference',
                   flip=False, return_confidence=False, min_region=0, region_connectivity=4, region_fill='neighbour', ignore_index=None,
-                  scales=None, scale_weights=None):
+                  scales=None, scale_weights=None, temperature=None):
     """A decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1] grayscale uint8, numpy or tensor) -> PhotoResult at the scaled size.
 
     DeepLab, blend='reference' (default): fit (stride default tile // 2, test.py:63), predict_image's sliding window on the uint8 fitted
@@ -200,7 +200,8 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     stride default its output tile; for DeepLab predict_image(blend='mean'), stride default tile // 2); no fit, no resize back.
     return_probs / return_confidence fill PhotoResult.probs / .confidence; flip=True adds the mirrored windows as a second member.
     scales / scale_weights: the multi-scale ensemble of predict_blend_mean on the scaled-size image, every scale in
-    [0.5, 2.0] relative to it; on a DeepLab it needs blend='mean', as flip does.
+    [0.5, 2.0] relative to it; on a DeepLab it needs blend='mean', as flip does.  temperature (None, a positive number, or 'meta' for
+    model.meta.temperature) divides the logits before every tile's softmax, under the same condition.
 
     min_region > 1: regions of the final mask below that many pixels are sieved (regions.sieve with region_connectivity, region_fill and
     ignore_index; one pass), PhotoResult.rgb is recoloured from the sieved mask and PhotoResult.n_sieved counts the replaced pixels.  A
@@ -219,12 +220,15 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     unet = model.meta.arch == 'unet'
     if not unet and blend == 'reference':
         asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence),
-                                ('scales', scales is not None), ('scale_weights', scale_weights is not None)) if v]
+                                ('scales', scales is not None), ('scale_weights', scale_weights is not None),
+                                ('temperature', temperature is not None)) if v]
         if asked:
             raise ValueError("%s needs blend='mean' on a DeepLab: the reference sliding-window stitch mixes logits and probabilities, its "
                              "scores are not probabilities" % ', '.join(asked))
+    from .inference import resolve_temperature
+    resolve_temperature(model, temperature)          # argument errors before any launch
     sieving = int(min_region) > 1
-    if sieving:                                      # argument errors before any launch
+    if sieving:
         regions._check_mask(torch.empty((1, 1), dtype=torch.uint8), region_connectivity, ignore_index)
         regions._fill_value(region_fill, ignore_index)
     L.init()
@@ -239,10 +243,11 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
                 'offset': 0}                      # Extractor.extract(fit=False): (img, w_scaled, h_scaled, 0)
         img = resize_area(_upload_photo(image, dev), h_s, w_s)      # at its own size: a relayout to [C,H,W]
         if unet:
-            got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights)
+            got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights,
+                                       temperature)
         else:
             got = predict_blend_mean(model, img, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales,
-                                     scale_weights)
+                                     scale_weights, temperature)
         if got is None:
             return None
         got = list(got) if isinstance(got, tuple) else [got]
@@ -277,9 +282,13 @@ class PhotoEvaluator:
 
     boundary_radius (an int, or 'auto' for boundary.default_radius of each image's scaled size): add() also accumulates the image's band
     counts (boundary.boundary_counts; no coverage overwrite applies to them), and add() / aggregate() return
-    boundary.boundary_scores' keys next to the four above.  None (default): nothing changes."""
+    boundary.boundary_scores' keys next to the four above.  None (default): nothing changes.
 
-    def __init__(self, n_classes, palette, ignore_index=None, boundary_radius=None):
+    calibration_bins (1..32): add() needs result.confidence (segment_photo(..., return_confidence=True)) and also accumulates the image's
+    reliability counts (calibration.reliability_counts; no coverage overwrite applies to them); add() / aggregate()
+    return 'ece', 'mce' and 'class_ece' next to the other keys.  None (default): nothing changes."""
+
+    def __init__(self, n_classes, palette, ignore_index=None, boundary_radius=None, calibration_bins=None):
         self.n_classes = int(n_classes)
         # with an ignore label (0..255) a ground-truth colour outside the palette is encoded as it, and only the other pixels are scored
         self.ignore_index = None if ignore_index is None else int(ignore_index)
@@ -294,11 +303,18 @@ class PhotoEvaluator:
             boundary._check_ignore(self.ignore_index)
         self.boundary_radius = boundary_radius
         self.boundary_counts = None        # int64 [C*C + 3C + 1] over the images added so far
+        self.calibration_bins = None
+        if calibration_bins is not None:
+            from . import calibration
+            self.calibration_bins = calibration._check_bins(calibration_bins)
+        self.reliability_counts = None     # int64 [3*C*bins + 3] over the images added so far
 
     def add(self, result, gt_rgb):
         """Encode the ground-truth RGB mask ([H,W,3] uint8, full size) at the result's scaled size (get_image(scale, INTER_NEAREST)) and
         score the result's mask against it.  A ground truth whose scaled size differs is an error (utils/evaluate.py:96-101).  Returns the
         image's {'f1', 'iou', 'mcc', 'cmatrix'}."""
+        if self.calibration_bins is not None and result.confidence is None:
+            raise ValueError('a PhotoEvaluator with calibration_bins needs result.confidence: segment_photo(..., return_confidence=True)')
         g = result.geometry
         h_s, w_s = scaled_size(gt_rgb.shape[0], gt_rgb.shape[1], result.tile, result.scale)
         if (h_s, w_s) != (g['h_scaled'], g['w_scaled']):
@@ -315,14 +331,21 @@ class PhotoEvaluator:
         if self.boundary_radius is not None:
             r = boundary.default_radius(h_s, w_s) if self.boundary_radius == 'auto' else self.boundary_radius
             band = boundary.boundary_counts(y_true, y_pred, self.n_classes, r, ign)
-        return self.add_counts(cm, plain, band)
+        rel = None
+        if self.calibration_bins is not None:
+            from . import calibration
+            rel = calibration.reliability_counts(result.confidence, y_pred, y_true, self.n_classes, self.calibration_bins, ign)
+        return self.add_counts(cm, plain, band, rel)
 
-    def add_counts(self, cm_coverage, cm_plain=None, boundary_counts=None):
+    def add_counts(self, cm_coverage, cm_plain=None, boundary_counts=None, reliability_counts=None):
         """Accumulate one image given its count matrices with and without the coverage overwrite (device tensors, or host arrays for
         counts made elsewhere); cm_plain is needed from the second image on.  boundary_counts: the image's band counts, needed exactly
-        when the evaluator has a boundary radius.  Returns the image's scores (those of cm_coverage, and of its own band counts)."""
+        when the evaluator has a boundary radius; reliability_counts: the image's reliability counts, needed exactly when it has
+        calibration_bins.  Returns the image's scores (those of cm_coverage, and of its own band counts)."""
         if (boundary_counts is None) != (self.boundary_radius is None):
             raise ValueError('add_counts: band counts are given exactly when the evaluator has a boundary_radius')
+        if (reliability_counts is None) != (self.calibration_bins is None):
+            raise ValueError('add_counts: reliability counts are given exactly when the evaluator has calibration_bins')
         if self.cm is None:
             self.cm = cm_coverage.clone() if torch.is_tensor(cm_coverage) else np.array(cm_coverage, dtype=np.int64)
         else:
@@ -337,6 +360,15 @@ class PhotoEvaluator:
             else:
                 self.boundary_counts += boundary_counts
             out.update(boundary.boundary_scores(boundary_counts, self.n_classes))
+        if reliability_counts is not None:
+            from . import calibration
+            if self.reliability_counts is None:
+                self.reliability_counts = (reliability_counts.clone() if torch.is_tensor(reliability_counts)
+                                           else np.array(reliability_counts, dtype=np.int64))
+            else:
+                self.reliability_counts += reliability_counts
+            r = calibration.reliability_scores(reliability_counts, self.n_classes, self.calibration_bins)
+            out.update(ece=r['ece'], mce=r['mce'], class_ece=r['class_ece'])
         return out
 
     def aggregate(self):
@@ -345,4 +377,8 @@ class PhotoEvaluator:
         out = metrics.scores(self.cm)
         if self.boundary_counts is not None:
             out.update(boundary.boundary_scores(self.boundary_counts, self.n_classes))
+        if self.reliability_counts is not None:
+            from . import calibration
+            r = calibration.reliability_scores(self.reliability_counts, self.n_classes, self.calibration_bins)
+            out.update(ece=r['ece'], mce=r['mce'], class_ece=r['class_ece'])
         return out
