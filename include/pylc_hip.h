@@ -974,6 +974,38 @@ int pylc_multiloss_stats_w(const float* logits, int pitch, const void* target, i
 int pylc_multiloss_bwd_w(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
                          const float* class_weights, const float* pixel_weights, const float* stats, float w_ce, float w_dice,
                          float w_focal, const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream);
+/* Soft targets: every pixel has a target ROW q_n of C non-negative numbers in place of a class index; the three
+ * terms are the ones above with the one-hot row o replaced by q (CE = sum u w_c q_c (lse - z_c) / sum u w_c q_c; Dice with
+ * I_c = sum u p_c q_c and count_c = sum u q_c; Focal = sum u sum_c q_c f(p_c + 1e-8) / sum u sum_c q_c).  The stats keep their layout and
+ * meaning (the class counts sum to sum u q), so pylc_multiloss_finalize_ex finalises them.  q is used AS GIVEN: it is never renormalised.
+ *   _soft: the rows come from a float32 [B,C,H,W] tensor `soft` read in place through its four strides in ELEMENTS (planar, channels-last,
+ *     a batch slice, a row of windows of a larger volume: any non-negative strides), pixel n = (b, y, x) of B = N / (H*W) images.
+ *     kind 0: the tensor holds q.  kind 1: it holds teacher logits t and q = softmax(inv_T * t), computed in registers; only the teacher
+ *     is softened -- the logits are not divided by T and nothing is scaled by T^2.  inv_T must be finite and > 0 (it is not read for
+ *     kind 0, but checked all the same).
+ *   _ls: q_c = (1 - smoothing) o_c + smoothing / C from a hard target that is read and judged exactly as by _w; 0 <= smoothing < 1.
+ * A pixel takes part when its row is valid and its weight is (pixel_weights may be NULL: every u_n = 1; otherwise the rules of _w).  A
+ * row of kind 0 that sums to exactly 0 is skipped silently; one with a negative, NaN or infinite entry, and a row of kind 1 with a
+ * non-finite inv_T * t_c, is skipped and counted in n_bad.  The row is judged before the weight.  Skipped pixels receive +0.0 in every
+ * stored channel of dlogits; no gradient is taken with respect to q.  A one-hot row (and smoothing == 0) gives the statistics of _w bit
+ * for bit.  PYLC_ERR_ARG, nothing launched: NULL logits / soft / target / stats / workspace / dlogits, C outside 2..PYLC_MAX_CLASSES, a
+ * kind other than 0 / 1, inv_T or smoothing out of range, H or W <= 0 or N no positive multiple of H*W, a negative stride, pitch < C,
+ * a misaligned buffer. */
+int pylc_multiloss_stats_soft(const float* logits, int pitch, long long N, int H, int W, int C, const float* soft, long long stride_b,
+                              long long stride_c, long long stride_h, long long stride_w, int kind, float inv_T,
+                              const float* class_weights, const float* pixel_weights, float* stats, float* workspace,
+                              unsigned long long* n_bad, void* stream);
+int pylc_multiloss_bwd_soft(const float* logits, int pitch, long long N, int H, int W, int C, const float* soft, long long stride_b,
+                            long long stride_c, long long stride_h, long long stride_w, int kind, float inv_T,
+                            const float* class_weights, const float* pixel_weights, const float* stats, float w_ce, float w_dice,
+                            float w_focal, const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream);
+int pylc_multiloss_stats_ls(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                            const float* class_weights, const float* pixel_weights, float smoothing, float* stats, float* workspace,
+                            unsigned long long* n_bad, void* stream);
+int pylc_multiloss_bwd_ls(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                          const float* class_weights, const float* pixel_weights, float smoothing, const float* stats, float w_ce,
+                          float w_dice, float w_focal, const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits,
+                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimiser: torch.nn.utils.clip_grad_norm_(params, 0.5) models/model.py:326 + torch.optim.AdamW

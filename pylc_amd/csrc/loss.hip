@@ -246,6 +246,200 @@ __global__ __launch_bounds__(256) void multiloss_bwd_kernel(const float* __restr
     if (amax_out != nullptr) amax_commit(gmax, amax_out);
 }
 
+// ---- soft targets (pylc_multiloss_*_soft, pylc_multiloss_*_ls) ----------------------------------------------------
+// A pair of kernels of their own next to the <C, TT, IGN, PW> ones, which stay as they are: the target of pixel n is a ROW q of C
+// non-negative floats, kept in registers next to z and p, and every term is its one-hot form with o_c replaced by q_c.  The row comes from
+// one of three sources (SRC): a float32 [B,C,H,W] volume read in place through its four strides (the planar case reads consecutive
+// addresses in consecutive lanes, class by class), teacher logits read the same way and put through softmax_px at inverse temperature
+// `par`, or a hard target (TT, judged as by the kernels above) smoothed by `par`.  The pixel weight is a run-time NULL test here (one
+// uniform branch; 1.0f is the multiplicative identity bit for bit), so the sources do not double the instantiations.
+// Forward arithmetic, ordered so that a one-hot row reproduces the statistics of the PW kernel above bit for bit: the CE addend of a class is
+// ((u w_c) q_c)(lse - z_c), the Dice one (u p_c) q_c, the count one u q_c, Focal is u * sum_c q_c f(x_c); the per-pixel sums start from
+// +0 and a one-hot row adds +-0 in every class but one, which changes no bit (-ffp-contract=off, nothing re-associated).
+enum { kSoftProbs = 0, kSoftLogits = 1, kSoftSmooth = 2 };
+
+struct SoftSrc {
+    const void* ptr;              // float volume / teacher logits, or the hard target
+    long long sb, sc, sh, sw;     // strides of the volume in elements
+    long long HW;                 // pixels of one image
+    int W;
+    int small;                    // N < 2^32: the pixel index splits with 32-bit divisions
+    float par;                    // kSoftLogits: 1 / T; kSoftSmooth: the smoothing
+    long long ignore;             // kSoftSmooth
+};
+
+// q of pixel n.  0: the row takes part; 1: skipped silently (a row that sums to 0, an ignored target); 2: skipped and counted
+template <int C, int SRC, typename TT>
+__device__ __forceinline__ int soft_row(const SoftSrc& s, long long n, float (&q)[C]) {
+    if constexpr (SRC == kSoftSmooth) {
+        const long long tl = (long long)static_cast<const TT*>(s.ptr)[n];
+        if (tl == s.ignore) return 1;
+        if ((unsigned long long)tl >= (unsigned long long)C) return 2;
+        const float off = s.par / (float)C, on = (1.f - s.par) + off;      // smoothing 0: exactly 1 and 0
+        const int t = (int)tl;
+#pragma unroll
+        for (int c = 0; c < C; ++c) q[c] = (c == t) ? on : off;
+        return 0;
+    } else {
+        long long b, y, x;
+        if (s.small) {
+            const unsigned nb = (unsigned)n / (unsigned)s.HW, r = (unsigned)n - nb * (unsigned)s.HW, ny = r / (unsigned)s.W;
+            b = nb, y = ny, x = r - ny * (unsigned)s.W;
+        } else {
+            b = n / s.HW;
+            const long long r = n - b * s.HW;
+            y = r / s.W, x = r - y * s.W;
+        }
+        const float* src = static_cast<const float*>(s.ptr) + b * s.sb + y * s.sh + x * s.sw;
+#pragma unroll
+        for (int c = 0; c < C; ++c) q[c] = src[c * s.sc];
+        bool bad = false;
+        if constexpr (SRC == kSoftProbs) {
+            float sum = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                bad |= !(q[c] >= 0.f && q[c] <= FLT_MAX);                   // negative, NaN, infinite
+                sum += q[c];
+            }
+            if (bad) return 2;
+            return sum == 0.f ? 1 : 0;                                     // non-negative addends: zero only when every entry is
+        } else {
+            float t[C], lse;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                t[c] = s.par * q[c];
+                bad |= !(fabsf(t[c]) <= FLT_MAX);
+            }
+            if (bad) return 2;
+            softmax_px<C>(t, q, lse);
+            return 0;
+        }
+    }
+}
+
+// the weight of pixel n (pw == NULL: 1).  0: takes part; 1: u == 0; 2: negative, NaN, infinite
+__device__ __forceinline__ int soft_weight(const float* __restrict__ pw, long long n, float& u) {
+    u = 1.f;
+    if (pw == nullptr) return 0;
+    u = pw[n];
+    if (u == 0.f) return 1;
+    return (u > 0.f && u <= FLT_MAX) ? 0 : 2;
+}
+
+template <int C, int SRC, typename TT>
+__global__ __launch_bounds__(256) void multiloss_stats_soft_kernel(const float* __restrict__ logits, int pitch, SoftSrc s, long long N,
+                                                                   const float* __restrict__ cw, const float* __restrict__ pw,
+                                                                   float* __restrict__ partial, unsigned long long* __restrict__ n_bad) {
+    __shared__ float red[4];
+    float acc[3 + 3 * C];
+#pragma unroll
+    for (int k = 0; k < 3 + 3 * C; ++k) acc[k] = 0.f;
+    unsigned int bad = 0;
+    for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long long)gridDim.x * blockDim.x) {
+        float q[C], u;
+        const int row = soft_row<C, SRC, TT>(s, n, q);                    // the row is judged first, as the target is
+        if (row != 0) { bad += row == 2; continue; }
+        const int wt = soft_weight(pw, n, u);
+        if (wt != 0) { bad += wt == 2; continue; }
+        float z[C], p[C], lse;
+        const float* src = logits + n * pitch;
+#pragma unroll
+        for (int c = 0; c < C; ++c) z[c] = src[c];
+        softmax_px<C>(z, p, lse);
+        float ce = 0.f, den = 0.f, fl = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float up = u * p[c];
+            acc[3 + c] += up * q[c];                  // I_c
+            acc[3 + C + c] += up;                     // sum u p_c
+            acc[3 + 2 * C + c] += u * q[c];           // sum u q_c
+            const float uwq = (u * (cw != nullptr ? cw[c] : 1.f)) * q[c];
+            ce += uwq * (lse - z[c]);
+            den += uwq;
+            const float x = p[c] + kFlEps, omx = 1.f - x;
+            fl += q[c] * (-kFlAlpha * omx * omx * logf(x));
+        }
+        acc[0] += ce;
+        acc[1] += den;
+        acc[2] += u * fl;
+    }
+    float* dst = partial + (size_t)blockIdx.x * (3 + 3 * C);
+#pragma unroll
+    for (int k = 0; k < 3 + 3 * C; ++k) {
+        const float v = block_sum_256(acc[k], red);
+        if (threadIdx.x == 0) dst[k] = v;
+    }
+    if (n_bad != nullptr) {
+        unsigned long long wave_bad = 0;
+        for (int l = 0; l < 64; ++l) wave_bad += (unsigned)__shfl((int)bad, l, 64);
+        if ((threadIdx.x & 63) == 0 && wave_bad != 0) atomicAdd(n_bad, wave_bad);
+    }
+}
+
+// per pixel, times grad_scale * u:
+//   CE    ce_norm (W p_c - w_c q_c),  W = sum_k w_k q_k
+//   Dice  w_d p_c (g_c - sum_k g_k p_k),  g_c = q_c A_c + B_c
+//   Focal w_f inv_n p_c (q_c f'(x_c) - sum_k q_k f'(x_k) p_k),  f'(x) = alpha gamma (1 - x) log x - alpha (1 - x)^2 / x
+// inv_n = 1 / sum of the class counts = 1 / sum u q, as on the IGN path; skipped pixels write a zero row as there.
+template <int C, int SRC, typename TT>
+__global__ __launch_bounds__(256) void multiloss_bwd_soft_kernel(const float* __restrict__ logits, int pitch, SoftSrc s, long long N,
+                                                                 const float* __restrict__ cw, const float* __restrict__ pw,
+                                                                 const float* __restrict__ stats, float w_ce, float w_d, float w_f,
+                                                                 const float* __restrict__ grad_scale, float* __restrict__ dlogits, int dpitch,
+                                                                 int Cstore, unsigned* __restrict__ amax_out, int zero16) {
+    float dA[C], dB[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float I = stats[3 + c], K = stats[3 + C + c] + stats[3 + 2 * C + c];
+        const float den = K + kDiceSmooth;
+        dA[c] = -2.f / den / (float)C;
+        dB[c] = (2.f * I + kDiceSmooth) / (den * den) / (float)C;
+    }
+    const float gs = grad_scale != nullptr ? grad_scale[0] : 1.f;
+    const double nv = stats_n_valid(stats, C);
+    const float fscale = w_f * (nv > 0.0 ? (float)(1.0 / nv) : 0.f);
+    const float ce_norm = stats[1] > 0.f ? w_ce / stats[1] : 0.f;
+    float gmax = 0.f;
+    for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long long)gridDim.x * blockDim.x) {
+        float q[C], u;
+        if (soft_row<C, SRC, TT>(s, n, q) != 0 || soft_weight(pw, n, u) != 0) {
+            float* zrow = dlogits + n * dpitch;
+            if (zero16) {
+                for (int c = 0; c < Cstore; c += 4) *reinterpret_cast<loss_f4*>(zrow + c) = loss_f4{0.f, 0.f, 0.f, 0.f};
+            } else {
+                for (int c = 0; c < Cstore; ++c) zrow[c] = 0.f;
+            }
+            continue;
+        }
+        const float gsu = gs * u;
+        float z[C], p[C], lse;
+        const float* src = logits + n * pitch;
+#pragma unroll
+        for (int c = 0; c < C; ++c) z[c] = src[c];
+        softmax_px<C>(z, p, lse);
+        float fq[C];                                   // q_c f'(x_c)
+        float wsum = 0.f, gdot = 0.f, fdot = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            wsum += (cw != nullptr ? cw[c] : 1.f) * q[c];
+            gdot += (q[c] * dA[c] + dB[c]) * p[c];
+            const float x = p[c] + kFlEps, omx = 1.f - x;
+            fq[c] = q[c] * (kFlAlpha * 2.f * omx * logf(x) - kFlAlpha * omx * omx / x);
+            fdot += fq[c] * p[c];
+        }
+        float* dst = dlogits + n * dpitch;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float w = cw != nullptr ? cw[c] : 1.f;
+            const float d = ce_norm * (wsum * p[c] - w * q[c]) + w_d * p[c] * ((q[c] * dA[c] + dB[c]) - gdot) + fscale * p[c] * (fq[c] - fdot);
+            dst[c] = gsu * d;
+            gmax = fmaxf(gmax, fabsf(gsu * d));
+        }
+        for (int c = C; c < Cstore; ++c) dst[c] = 0.f;
+    }
+    if (amax_out != nullptr) amax_commit(gmax, amax_out);
+}
+
 }  // namespace pylc
 
 using namespace pylc;
@@ -418,4 +612,152 @@ extern "C" int pylc_multiloss_bwd_w(const float* logits, int pitch, const void* 
     PYLC_REQUIRE((reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0, "multiloss_bwd_w: pixel_weights is not 4-byte aligned");
     return multiloss_bwd_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, pixel_weights, stats, 1.0, w_ce, w_dice,
                               w_focal, grad_scale, dlogits, dpitch, amax_bits, stream);
+}
+
+// ---- soft targets: the host side -----------------------------------------------------------------------------------------------------------
+static int multiloss_stats_soft_impl(const float* logits, int pitch, const SoftSrc& src, int kind, int target_bytes, long long N, int C,
+                                     const float* cw, const float* pw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
+    hipStream_t st = as_stream(stream);
+    const int blocks = (int)(cdiv<long long>(N, 256) < kLossBlocks ? cdiv<long long>(N, 256) : kLossBlocks);
+#define LAUNCH_SOFT_T(CC, SRC, TT)                                                                                                          \
+    hipLaunchKernelGGL((multiloss_stats_soft_kernel<CC, SRC, TT>), dim3(blocks), dim3(256), 0, st, logits, pitch, src, N, cw, pw, workspace, \
+                       n_bad)
+    if (kind == kSoftProbs) {
+#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftProbs, float)
+        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
+#undef LAUNCH_SOFT
+    } else if (kind == kSoftLogits) {
+#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftLogits, float)
+        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
+#undef LAUNCH_SOFT
+    } else if (target_bytes == 8) {
+#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftSmooth, long long)
+        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
+#undef LAUNCH_SOFT
+    } else {
+#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftSmooth, unsigned char)
+        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
+#undef LAUNCH_SOFT
+    }
+#undef LAUNCH_SOFT_T
+    PYLC_LAUNCH_CHECK();
+    const int K = 3 + 3 * C;
+    hipLaunchKernelGGL(column_sum_kernel, dim3(cdiv(K, 8)), dim3(256), 0, st, workspace, blocks, K, stats);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+static int multiloss_bwd_soft_impl(const float* logits, int pitch, const SoftSrc& src, int kind, int target_bytes, long long N, int C,
+                                   const float* cw, const float* pw, const float* stats, float w_ce, float w_dice, float w_focal,
+                                   const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    hipStream_t st = as_stream(stream);
+    if (amax_bits != nullptr) PYLC_HIP(hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st));
+    const int blocks = (int)(cdiv<long long>(N, 256) < 4096 ? cdiv<long long>(N, 256) : 4096);
+    const int Cstore = ((C + 3) & ~3) <= dpitch ? ((C + 3) & ~3) : C;
+    const int zero16 = dpitch % 4 == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
+#define LAUNCH_SOFT_T(CC, SRC, TT)                                                                                                       \
+    hipLaunchKernelGGL((multiloss_bwd_soft_kernel<CC, SRC, TT>), dim3(blocks), dim3(256), 0, st, logits, pitch, src, N, cw, pw, stats, w_ce, \
+                       w_dice, w_focal, grad_scale, dlogits, dpitch, Cstore, amax_bits, zero16)
+    if (kind == kSoftProbs) {
+#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftProbs, float)
+        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
+#undef LAUNCH_SOFT
+    } else if (kind == kSoftLogits) {
+#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftLogits, float)
+        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
+#undef LAUNCH_SOFT
+    } else if (target_bytes == 8) {
+#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftSmooth, long long)
+        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
+#undef LAUNCH_SOFT
+    } else {
+#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftSmooth, unsigned char)
+        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
+#undef LAUNCH_SOFT
+    }
+#undef LAUNCH_SOFT_T
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+// the argument rules the four entry points share; `who` is a string literal
+#define PYLC_SOFT_VOLUME_ARGS(who)                                                                                                        \
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, who ": n_classes=%d unsupported (2..%d)", C, MAXC);                                                  \
+    PYLC_REQUIRE(kind == kSoftProbs || kind == kSoftLogits, who ": kind=%d (0: probabilities, 1: teacher logits)", kind);                  \
+    PYLC_REQUIRE(inv_T > 0.f && inv_T <= FLT_MAX, who ": inv_T=%g is not a positive finite number", (double)inv_T);                        \
+    PYLC_REQUIRE(soft, who ": soft is NULL");                                                                                              \
+    PYLC_REQUIRE(H > 0 && W > 0, who ": H=%d or W=%d is not positive", H, W);                                                              \
+    PYLC_REQUIRE(N > 0 && N % ((long long)H * W) == 0, who ": N=%lld is not a positive multiple of H*W=%lld", N, (long long)H * W);        \
+    PYLC_REQUIRE(stride_b >= 0 && stride_c >= 0 && stride_h >= 0 && stride_w >= 0, who ": a stride is negative (%lld, %lld, %lld, %lld)",  \
+                 stride_b, stride_c, stride_h, stride_w)
+
+static SoftSrc soft_volume(const float* soft, long long sb, long long sc, long long sh, long long sw, long long N, int H, int W, float inv_T) {
+    SoftSrc s{};
+    s.ptr = soft, s.sb = sb, s.sc = sc, s.sh = sh, s.sw = sw, s.HW = (long long)H * W, s.W = W, s.small = N < (1ll << 32), s.par = inv_T;
+    return s;
+}
+
+static SoftSrc soft_smooth(const void* target, float smoothing, long long ignore) {
+    SoftSrc s{};
+    s.ptr = target, s.par = smoothing, s.ignore = ignore, s.HW = 1, s.W = 1;
+    return s;
+}
+
+extern "C" int pylc_multiloss_stats_soft(const float* logits, int pitch, long long N, int H, int W, int C, const float* soft, long long stride_b,
+                                         long long stride_c, long long stride_h, long long stride_w, int kind, float inv_T, const float* cw,
+                                         const float* pixel_weights, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
+    PYLC_SOFT_VOLUME_ARGS("multiloss_stats_soft");
+    PYLC_REQUIRE(pitch >= C, "multiloss_stats_soft: pitch=%d below n_classes=%d", pitch, C);
+    PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_soft: logits, stats or workspace is NULL");
+    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(soft) & 3) == 0 && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0 &&
+                     (reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0,
+                 "multiloss_stats_soft: a buffer is not aligned to its element");
+    return multiloss_stats_soft_impl(logits, pitch, soft_volume(soft, stride_b, stride_c, stride_h, stride_w, N, H, W, inv_T), kind, 4, N, C, cw,
+                                     pixel_weights, stats, workspace, n_bad, stream);
+}
+
+extern "C" int pylc_multiloss_bwd_soft(const float* logits, int pitch, long long N, int H, int W, int C, const float* soft, long long stride_b,
+                                       long long stride_c, long long stride_h, long long stride_w, int kind, float inv_T, const float* cw,
+                                       const float* pixel_weights, const float* stats, float w_ce, float w_dice, float w_focal,
+                                       const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    PYLC_SOFT_VOLUME_ARGS("multiloss_bwd_soft");                                                          // before amax_bits is cleared
+    PYLC_REQUIRE(pitch >= C && dpitch >= C, "multiloss_bwd_soft: pitch=%d or dpitch=%d below n_classes=%d", pitch, dpitch, C);
+    PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_soft: logits, stats or dlogits is NULL");
+    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(soft) & 3) == 0 && (reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0,
+                 "multiloss_bwd_soft: a buffer is not aligned to its element");
+    return multiloss_bwd_soft_impl(logits, pitch, soft_volume(soft, stride_b, stride_c, stride_h, stride_w, N, H, W, inv_T), kind, 4, N, C, cw,
+                                   pixel_weights, stats, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, amax_bits, stream);
+}
+
+extern "C" int pylc_multiloss_stats_ls(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                                       const float* cw, const float* pixel_weights, float smoothing, float* stats, float* workspace,
+                                       unsigned long long* n_bad, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats_ls: n_classes=%d unsupported (2..%d)", C, MAXC);
+    PYLC_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "multiloss_stats_ls: smoothing=%g outside [0, 1)", (double)smoothing);
+    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_stats_ls: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
+    PYLC_REQUIRE(target, "multiloss_stats_ls: target is NULL");
+    PYLC_REQUIRE(pitch >= C, "multiloss_stats_ls: pitch=%d below n_classes=%d", pitch, C);
+    PYLC_REQUIRE(N > 0, "multiloss_stats_ls: N=%lld is not positive", N);
+    PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_ls: logits, stats or workspace is NULL");
+    PYLC_REQUIRE((target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0) && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0 &&
+                     (reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0,
+                 "multiloss_stats_ls: a buffer is not aligned to its element");
+    return multiloss_stats_soft_impl(logits, pitch, soft_smooth(target, smoothing, (long long)ignore_index), kSoftSmooth, target_bytes, N, C, cw,
+                                     pixel_weights, stats, workspace, n_bad, stream);
+}
+
+extern "C" int pylc_multiloss_bwd_ls(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                                     const float* cw, const float* pixel_weights, float smoothing, const float* stats, float w_ce, float w_dice,
+                                     float w_focal, const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd_ls: n_classes=%d unsupported (2..%d)", C, MAXC);   // before amax_bits is cleared
+    PYLC_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "multiloss_bwd_ls: smoothing=%g outside [0, 1)", (double)smoothing);
+    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_bwd_ls: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
+    PYLC_REQUIRE(target, "multiloss_bwd_ls: target is NULL");
+    PYLC_REQUIRE(pitch >= C && dpitch >= C, "multiloss_bwd_ls: pitch=%d or dpitch=%d below n_classes=%d", pitch, dpitch, C);
+    PYLC_REQUIRE(N > 0, "multiloss_bwd_ls: N=%lld is not positive", N);
+    PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_ls: logits, stats or dlogits is NULL");
+    PYLC_REQUIRE(target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0, "multiloss_bwd_ls: an int64 target is not 8-byte aligned");
+    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0, "multiloss_bwd_ls: pixel_weights is not 4-byte aligned");
+    return multiloss_bwd_soft_impl(logits, pitch, soft_smooth(target, smoothing, (long long)ignore_index), kSoftSmooth, target_bytes, N, C, cw,
+                                   pixel_weights, stats, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, amax_bits, stream);
 }

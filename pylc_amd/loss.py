@@ -9,7 +9,8 @@ from .runtime import runtime
 
 
 class MultiLoss(nn.Module):
-    """MultiLoss(loss_weights={'weighted','weights','ce','dice','focal'}, schema={'n_classes','class_codes','class_labels'}, ignore_index=None).
+    """MultiLoss(loss_weights={'weighted','weights','ce','dice','focal'}, schema={'n_classes','class_codes','class_labels'}, ignore_index=None,
+    label_smoothing=0.0).
 
     ignore_index (an int, not in the reference): pixels whose target equals it are left out of all three terms and get a zero gradient;
     targets may then be uint8 or int64.  Any other target outside 0..n_classes-1 is skipped too and counted in `.bad_targets` (an int64
@@ -20,12 +21,24 @@ class MultiLoss(nn.Module):
     (CE = sum u w_t nll / sum u w_t, Dice over u-weighted sums, Focal = sum u f / sum u); u_n == 0 leaves the pixel out, negative, NaN
     and infinite weights are left out and counted in `.bad_targets`.  None: the paths without weights, unchanged.
 
+    Soft targets (not in the reference): a float32 4-D `target` [B,C,H,W] is a probability volume -- a row q_n of C
+    non-negative numbers per pixel in place of a class index, every term with the one-hot row replaced by q (CE = sum u w_c q_c (-log p_c)
+    / sum u w_c q_c, Dice with I_c = sum u p_c q_c and counts sum u q_c, Focal = sum u sum_c q_c f(p_c) / sum u sum_c q_c).  The volume is
+    read in place through its strides (a window view of a whole photograph's volume costs no copy) and is used as given: rows are NOT
+    renormalised; a row that sums to 0 leaves its pixel out (ignore_index does not apply), a row with a negative, NaN or infinite entry is
+    left out and counted in `.bad_targets`.  distill(pred, teacher_logits, temperature) takes q = softmax(teacher_logits / temperature)
+    in the kernel.  label_smoothing (0 <= eps < 1) smooths HARD targets in forward() only, q_c = (1 - eps) o_c + eps / C; ce_loss,
+    dice_loss, focal_loss and all_losses -- the validation terms -- stay unsmoothed.
+
     forward(pred, target) -> 0-d tensor (ce_w*CE + dice_w*Dice + focal_w*Focal) with grad; side effects
     .ce / .dsc / .fl hold the three terms (loss.py:107-112).  One kernel pass computes all three."""
 
-    def __init__(self, loss_weights, schema, ignore_index=None):
+    def __init__(self, loss_weights, schema, ignore_index=None, label_smoothing=0.0):
         super().__init__()
         self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.label_smoothing = float(label_smoothing)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError('label_smoothing must lie in [0, 1), got %r' % (label_smoothing,))
         self.bad_targets = None
         self.n_classes = schema['n_classes']
         self.codes = schema.get('class_codes')
@@ -53,17 +66,46 @@ class MultiLoss(nn.Module):
         if pred.device != target.device:
             raise ValueError('input and target must be in the same device. Got: {} and {}'.format(pred.device, target.device))
 
-    def _all(self, pred, target, w_ce, w_d, w_f, pixel_weights=None):
-        self._check(pred, target)
-        cw = self.weights if self.weighted else None
-        if self.ignore_index is None and pixel_weights is None:
-            return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group)
+    def _bad(self, pred):
         if self.bad_targets is None or self.bad_targets.device != pred.device:
             self.bad_targets = torch.zeros(1, dtype=torch.int64, device=pred.device)
-        return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group, self.ignore_index, self.bad_targets, pixel_weights)
+        return self.bad_targets
+
+    def _all(self, pred, target, w_ce, w_d, w_f, pixel_weights=None, smoothing=0.0):
+        if torch.is_tensor(target) and target.dim() == 4 and target.is_floating_point():
+            return self._soft(pred, target, 'probs', 1.0, w_ce, w_d, w_f, pixel_weights)
+        self._check(pred, target)
+        cw = self.weights if self.weighted else None
+        if smoothing != 0.0:
+            return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group, self.ignore_index, self._bad(pred), pixel_weights,
+                                 label_smoothing=smoothing)
+        if self.ignore_index is None and pixel_weights is None:
+            return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group)
+        return ops.multiloss(pred, target, cw, w_ce, w_d, w_f, runtime.sync_group, self.ignore_index, self._bad(pred), pixel_weights)
+
+    def _soft(self, pred, soft, kind, temperature, w_ce, w_d, w_f, pixel_weights=None):
+        if not torch.is_tensor(pred):
+            raise TypeError('Input type is not a torch.Tensor. Got {}'.format(type(pred)))
+        if pred.dim() != 4 or pred.size(1) != self.n_classes:
+            raise ValueError('Invalid input shape, we expect Bx{}xHxW. Got: {}'.format(self.n_classes, tuple(pred.shape)))
+        if not torch.is_tensor(soft) or soft.dtype != torch.float32 or tuple(soft.shape) != tuple(pred.shape):
+            raise ValueError('Expected a float32 soft target of the prediction\'s shape {}. Got: {}'.format(
+                tuple(pred.shape), (soft.dtype, tuple(soft.shape)) if torch.is_tensor(soft) else type(soft)))
+        if pred.device != soft.device:
+            raise ValueError('input and target must be in the same device. Got: {} and {}'.format(pred.device, soft.device))
+        cw = self.weights if self.weighted else None
+        return ops.multiloss(pred, None, cw, w_ce, w_d, w_f, runtime.sync_group, None, self._bad(pred), pixel_weights, soft_target=soft,
+                             soft_kind=kind, temperature=temperature)
 
     def forward(self, pred, target, pixel_weights=None):
-        losses = self._all(pred, target, self.ce_weight, self.dsc_weight, self.fl_weight, pixel_weights)
+        losses = self._all(pred, target, self.ce_weight, self.dsc_weight, self.fl_weight, pixel_weights, self.label_smoothing)
+        self.ce, self.dsc, self.fl = losses[1].detach(), losses[2].detach(), losses[3].detach()
+        return losses[0]
+
+    def distill(self, pred, teacher_logits, temperature=1.0, pixel_weights=None):
+        """forward() against q = softmax(teacher_logits / temperature), float32 [B,C,H,W] read in place and softened in the kernel.  Only
+        the teacher is softened: pred is not divided by the temperature and the loss is not multiplied by its square."""
+        losses = self._soft(pred, teacher_logits, 'logits', temperature, self.ce_weight, self.dsc_weight, self.fl_weight, pixel_weights)
         self.ce, self.dsc, self.fl = losses[1].detach(), losses[2].detach(), losses[3].detach()
         return losses[0]
 

@@ -57,6 +57,8 @@ class Meta:
         #                                    distance d to the nearest pixel of another class within `radius` (boundary.border_profile)
         self.temperature = None            # None, or the temperature fitted on the last validation pass (trainer(calibration_bins=...), DESIGN.md
         #                                    5.20): what the inference keyword temperature='meta' divides the logits by
+        self.label_smoothing = 0.0         # eps in [0, 1): training steps on hard targets run against (1 - eps) one_hot + eps / C;
+        #                                    Model.eval stays unsmoothed.  0.0: the step as it was
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise AttributeError('unknown Meta field %r' % k)
@@ -200,7 +202,7 @@ class Model:
             loss_weights={'weighted': m.weighted, 'weights': m.weights, 'ce': m.ce_weight, 'dice': m.dice_weight,
                           'focal': m.focal_weight},
             schema={'n_classes': m.n_classes, 'class_codes': m.class_codes, 'class_labels': m.class_labels},
-            ignore_index=m.ignore_index).to(self.device)
+            ignore_index=m.ignore_index, label_smoothing=getattr(m, 'label_smoothing', 0.0) or 0.0).to(self.device)
         ign = None if m.ignore_index is None else int(m.ignore_index)
         if self.scores is not None and self.scores.ignore_index != ign:
             self.scores.ignore_index, self.scores.counts = ign, None          # (the counts gain or lose the cell of the ignored pixels)
@@ -289,20 +291,65 @@ class Model:
         return y.contiguous()
 
     # ---- the three hot-path entry points ---------------------------------------------------------------------
-    def train(self, x, y, pixel_weights=None):
+    def _soft_target(self, y):
+        """A float [B,C,H,W] target on the device, cropped on its last two dimensions like a mask -- as a VIEW: the loss kernels read it
+        through its strides, so a window cut out of a whole photograph's probability volume is never copied."""
+        if y.dim() != 4 or y.shape[1] != self.meta.n_classes:
+            raise ValueError('a soft target is a float [B,%d,H,W] tensor, got %s' % (self.meta.n_classes, tuple(y.shape)))
+        if self._border is not None:
+            raise ValueError('Meta.border_weight needs a mask to take class borders from: it cannot be combined with a soft target')
+        y = y.to(self.device, non_blocking=True)
+        if y.dtype != torch.float32:
+            y = y.float()
+        if self.meta.arch == 'unet':
+            p = self.meta.pad_size
+            y = y[:, :, p:y.shape[2] - p, p:y.shape[3] - p]
+        return y
+
+    def _soft_weights(self, q, pixel_weights):
+        if pixel_weights is None:
+            return None
+        if not torch.is_tensor(pixel_weights) or pixel_weights.dim() != 3:
+            raise ValueError('pixel_weights must be a [B,H,W] tensor')
+        u = self.crop_target(pixel_weights.to(self.device, non_blocking=True).float())
+        if tuple(u.shape) != (q.shape[0], q.shape[2], q.shape[3]):
+            raise ValueError('pixel_weights %s do not match the target %s' % (tuple(pixel_weights.shape), tuple(q.shape)))
+        return u
+
+    def train(self, x, y, pixel_weights=None, soft='probs', temperature=1.0):
         """One optimisation step (model.py:282-336).  pixel_weights (not in the reference): a float [B,H,W] map of the tiles' size, one
         weight per pixel of the loss (a confidence map, say); it is cropped like the target and multiplied into Meta.border_weight's map
-        where that is set.  Model.eval stays unweighted: validation losses remain comparable between runs."""
+        where that is set.  Model.eval stays unweighted: validation losses remain comparable between runs.
+
+        A floating-point [B,C,H,W] y is a SOFT target, cropped on its last two dimensions for the U-Net and read in
+        place: soft='probs', a row of C non-negative numbers per pixel, used as given (not renormalised; a row of zeros leaves the pixel
+        out); soft='logits', a teacher's logits, softened in the kernel by `temperature` -- a positive number, or 'meta' for this model's
+        meta.temperature (the value a calibrated validation pass stored; a student loaded from its teacher's checkpoint carries it).
+        Meta.label_smoothing smooths hard targets only."""
+        soft_y = torch.is_tensor(y) and y.dim() == 4 and y.is_floating_point()
+        if soft_y:
+            if soft not in ('probs', 'logits'):
+                raise ValueError("soft is 'probs' or 'logits', got %r" % (soft,))
+            if soft == 'logits':
+                from .inference import resolve_temperature
+                resolve_temperature(self, temperature)                      # argument errors before any launch
+                temperature = 1.0 if temperature is None else self.meta.temperature if isinstance(temperature, str) else float(temperature)
+            q = self._soft_target(y)
         self.net.train()       # (parameter ranges / prepared filters are current: refreshed by every optimiser step and state load)
         if getattr(self.net, 'freeze_bn', False) and ops.nplanes() == 1:
             raise ValueError('freeze_bn is not available in conv precision mode 3: its half activations are scaled with range bounds '
                              'taken from batch statistics, which a frozen BatchNorm does not compute')
         self._ranges_checked = False
         x4 = self.pack_input(x)
-        y = self._target(y)
-        u = self._train_weights(y, pixel_weights)          # None without Meta.border_weight and without a map: the step as it was
-        y_hat = self.net(x4)
-        loss = self.crit(y_hat, y) if u is None else self.crit(y_hat, y, u)
+        if soft_y:
+            u = self._soft_weights(q, pixel_weights)
+            y_hat = self.net(x4)
+            loss = self.crit(y_hat, q, u) if soft == 'probs' else self.crit.distill(y_hat, q, temperature, u)
+        else:
+            y = self._target(y)
+            u = self._train_weights(y, pixel_weights)          # None without Meta.border_weight and without a map: the step as it was
+            y_hat = self.net(x4)
+            loss = self.crit(y_hat, y) if u is None else self.crit(y_hat, y, u)
         self.loss.push(torch.stack((self.crit.ce, self.crit.dsc, self.crit.fl)))
         self.optim.zero_grad()
         if runtime.sync_group is not None:
@@ -377,9 +424,9 @@ class Model:
             n_bad = int(bad.item())
             if n_bad:
                 bad.zero_()
-                if self.meta.ignore_index is None:      # (the counter exists without an index only where pixel weights were given)
-                    raise ValueError('%d pixels since the last report hold a target outside 0..%d or a negative, NaN or infinite weight'
-                                     % (n_bad, self.meta.n_classes - 1))
+                if self.meta.ignore_index is None:      # (the counter exists without an index only where pixel weights or soft targets were given)
+                    raise ValueError('%d pixels since the last report hold a target outside 0..%d, a negative, NaN or infinite weight, or a '
+                                     'soft-target row with a negative, NaN or infinite entry' % (n_bad, self.meta.n_classes - 1))
                 raise ValueError('%d targets since the last report lie outside 0..%d and are not ignore_index=%d'
                                  % (n_bad, self.meta.n_classes - 1, self.meta.ignore_index))
         if self._best_by == 'iou' and self.scores is None:

@@ -498,7 +498,18 @@ class MultiLossFn(torch.autograd.Function):
     pixel_weights (float32 [B,H,W] on the logits' device; None: the paths above, untouched): a weight u_n per pixel (pylc_multiloss_*_w,
     DESIGN.md section 5.16) -- a saved tensor, no gradient flows into it.  A pixel with u_n == 0 is skipped like an ignored one; negative,
     NaN and infinite weights are skipped and counted in `bad`.  Without an ignore_index the kernels get INT32_MIN as the ignore value, which
-    no uint8 target and no class index equals."""
+    no uint8 target and no class index equals.
+
+    Soft targets (with every keyword below at its default the paths above run call for call):
+    soft_target, a float32 [B,C,H,W] tensor on the logits' device, replaces `target` (pass None for it) by a row q_n of C non-negative
+    numbers per pixel -- soft_kind='probs': the tensor holds q; 'logits': it holds teacher logits t and q = softmax(t / temperature), taken
+    in registers (pylc_multiloss_*_soft).  Only the teacher is softened: the logits are not divided by the temperature and the loss is not
+    scaled by its square.  The tensor is read IN PLACE through its four strides (planar, channels-last, a batch slice, a row of windows
+    unfolded out of a whole photograph's volume): no contiguous copy is made, and it is saved as it came.  q is used as given and is NOT
+    renormalised: CE divides by sum u w_c q_c, Focal by sum u q_c.  A row that sums to exactly 0 leaves its pixel out; a row with a
+    negative, NaN or infinite entry (a non-finite teacher logit) leaves it out and is counted in `bad`.  No gradient flows into q.
+    label_smoothing (0 <= eps < 1, hard targets only): q_c = (1 - eps) o_c + eps / C through pylc_multiloss_*_ls, the target read and
+    judged as on the paths above."""
 
     NO_IGNORE = -2 ** 31
 
@@ -512,19 +523,56 @@ class MultiLossFn(torch.autograd.Function):
 
 
 class LossState:
-    """cfg: (n_global or None, w_ce, w_dice, w_focal, group); ignore: the ignore label the kernels ran with (None: the plain path)."""
-    __slots__ = ('cfg', 'ignore')
+    """cfg: (n_global or None, w_ce, w_dice, w_focal, group); ignore: the ignore label the kernels ran with (None: the plain path);
+    soft: None, or where the target rows came from -- ('probs', 1.0) / ('logits', 1 / T): the saved `target` is the soft tensor, read through
+    its strides; ('smooth', eps): a hard target smoothed by eps."""
+    __slots__ = ('cfg', 'ignore', 'soft')
 
-    def __init__(self, cfg, ignore=None):
-        self.cfg, self.ignore = cfg, ignore
+    def __init__(self, cfg, ignore=None, soft=None):
+        self.cfg, self.ignore, self.soft = cfg, ignore, soft
 
 
-def multiloss_forward(needs, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index=None, bad=None, pixel_weights=None):
-    """Saves (logits, target, stats, class_weights[, pixel_weights])."""
+SOFT_KINDS = {'probs': 0, 'logits': 1}
+
+
+def _check_bad(bad, logits):
+    if bad is not None and (bad.dtype != torch.int64 or bad.numel() != 1 or bad.device != logits.device):
+        raise L.PylcError('bad must be an int64 [1] tensor on the device of the logits')
+
+
+def _check_pixel_weights(pixel_weights, logits):
+    b, c, h, w = logits.shape
+    if (not torch.is_tensor(pixel_weights) or pixel_weights.dtype != torch.float32 or tuple(pixel_weights.shape) != (b, h, w)
+            or pixel_weights.device != logits.device):
+        raise L.PylcError('pixel_weights must be float32 [B,H,W] matching the logits, on their device')
+    return pixel_weights.detach().contiguous()
+
+
+def soft_inv_temperature(temperature):
+    """1 / T of a positive finite temperature (PylcError otherwise)"""
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        t = float('nan')
+    if not (0.0 < t < float('inf')) or not (0.0 < 1.0 / t < 3.0e38):
+        raise L.PylcError('temperature must be a positive finite number, got %r' % (temperature,))
+    return 1.0 / t
+
+
+def _soft_strides(soft):
+    return tuple(int(v) for v in soft.stride())
+
+
+def multiloss_forward(needs, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index=None, bad=None, pixel_weights=None,
+                      soft_target=None, soft_kind='probs', temperature=1.0, label_smoothing=0.0):
+    """Saves (logits, target, stats, class_weights[, pixel_weights]); with a soft_target that tensor, as it came, is the saved target."""
     L.init()
     logits = as_nhwc(logits)
     b, c, h, w = logits.shape
     n = b * h * w
+    if soft_target is not None or label_smoothing != 0.0:
+        return _multiloss_forward_soft(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights,
+                                       soft_target, soft_kind, temperature, label_smoothing)
     target = target.contiguous()
     if pixel_weights is not None:
         if (not torch.is_tensor(pixel_weights) or pixel_weights.dtype != torch.float32 or tuple(pixel_weights.shape) != (b, h, w)
@@ -586,6 +634,61 @@ def _multiloss_forward_ignore(logits, target, class_weights, w_ce, w_dice, w_foc
     return losses, saved, LossState((None, w_ce, w_dice, w_focal, group), ignore_index), ()
 
 
+def _multiloss_forward_soft(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights, soft_target,
+                            soft_kind, temperature, label_smoothing):
+    """The soft-target paths of multiloss_forward: a volume or teacher logits (pylc_multiloss_stats_soft), or a smoothed hard target
+    (pylc_multiloss_stats_ls); the statistics exchange and the finalisation are those of _multiloss_forward_ignore."""
+    b, c, h, w = logits.shape
+    n = b * h * w
+    dev = logits.device
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise L.PylcError('label_smoothing must lie in [0, 1), got %r' % (label_smoothing,))
+    _check_bad(bad, logits)
+    if pixel_weights is not None:
+        pixel_weights = _check_pixel_weights(pixel_weights, logits)
+    if soft_target is not None:
+        if eps != 0.0:
+            raise L.PylcError('label_smoothing applies to hard targets: it cannot be combined with a soft_target')
+        if target is not None:
+            raise L.PylcError('pass target=None with a soft_target: the rows of the soft tensor are the target')
+        if ignore_index is not None:
+            raise L.PylcError('ignore_index has no meaning with a soft_target: a row that sums to 0 leaves its pixel out')
+        if soft_kind not in SOFT_KINDS:
+            raise L.PylcError("soft_kind is 'probs' or 'logits', got %r" % (soft_kind,))
+        inv_t = soft_inv_temperature(temperature)
+        if (not torch.is_tensor(soft_target) or soft_target.dtype != torch.float32 or tuple(soft_target.shape) != (b, c, h, w)
+                or soft_target.device != dev):
+            raise L.PylcError('soft_target must be float32 [B,C,H,W] matching the logits, on their device')
+        soft_target = soft_target.detach()                      # a view as it came: read through its strides, never copied
+        state_soft = (soft_kind, inv_t if soft_kind == 'logits' else 1.0)
+    else:
+        if target is None or target.dtype not in (torch.uint8, torch.int64) or tuple(target.shape) != (b, h, w):
+            raise L.PylcError('target must be uint8 or int64 [B,H,W] matching the logits')
+        target = target.contiguous()
+        ignore_index = MultiLossFn.NO_IGNORE if ignore_index is None else int(ignore_index)
+        state_soft = ('smooth', eps)
+    st = stream()
+    k = 3 + 3 * c
+    stats = torch.empty(k + (2 if group is not None else 0), device=dev)         # (the shard pair rides along as on the plain path)
+    ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
+    if soft_target is not None:
+        check(lib.pylc_multiloss_stats_soft(ptr(logits), pitch_of(logits), n, h, w, c, ptr(soft_target), *_soft_strides(soft_target),
+                                            SOFT_KINDS[soft_kind], state_soft[1], ptr(class_weights), ptr(pixel_weights), ptr(stats), ptr(ws),
+                                            ptr(bad), st))
+    else:
+        check(lib.pylc_multiloss_stats_ls(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
+                                          ptr(class_weights), ptr(pixel_weights), eps, ptr(stats), ptr(ws), ptr(bad), st))
+    if group is not None:
+        stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
+        _runtime.sync_all_reduce(stats, group)
+        note_shard_pair(stats[k:], dist.get_world_size(group))
+    losses = torch.empty(4, device=dev)
+    check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))      # sum u q: from the reduced class counts
+    saved = (logits, target if soft_target is None else soft_target, stats, class_weights) + (() if pixel_weights is None else (pixel_weights,))
+    return losses, saved, LossState((None, w_ce, w_dice, w_focal, group), ignore_index, state_soft), ()
+
+
 def multiloss_backward(state, saved, needs, dlosses):
     logits, target, stats, cw = saved[:4]
     pw = saved[4] if len(saved) > 4 else None
@@ -599,7 +702,15 @@ def multiloss_backward(state, saved, needs, dlosses):
     dl = empty_nhwc(b, c, h, w, logits.device, cp)
     amax = torch.empty(1, dtype=torch.int32, device=logits.device) if ranges_needed() and _runtime.fused_grad_ranges else None
     ignore = state.ignore
-    if ignore is None:
+    soft = getattr(state, 'soft', None)
+    if soft is not None and soft[0] == 'smooth':
+        check(lib.pylc_multiloss_bwd_ls(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw), ptr(pw),
+                                        soft[1], ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
+    elif soft is not None:
+        check(lib.pylc_multiloss_bwd_soft(ptr(logits), pitch_of(logits), n, h, w, c, ptr(target), *_soft_strides(target), SOFT_KINDS[soft[0]],
+                                          soft[1], ptr(cw), ptr(pw), ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax),
+                                          stream()))
+    elif ignore is None:
         check(lib.pylc_multiloss_bwd(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(cw), ptr(stats), n_global,
                                      w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
     elif pw is None:
@@ -613,8 +724,14 @@ def multiloss_backward(state, saved, needs, dlosses):
     return (dl,)
 
 
-def multiloss(logits, target, class_weights, w_ce, w_dice, w_focal, group=None, ignore_index=None, bad=None, pixel_weights=None):
-    return MultiLossFn.apply(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights)
+def multiloss(logits, target, class_weights, w_ce, w_dice, w_focal, group=None, ignore_index=None, bad=None, pixel_weights=None,
+              soft_target=None, soft_kind='probs', temperature=1.0, label_smoothing=0.0):
+    """[total, ce, dice, focal] (MultiLossFn).  soft_target / soft_kind / temperature / label_smoothing: the soft-target paths described
+    there; at their defaults the call is the one it was."""
+    if soft_target is None and label_smoothing == 0.0:
+        return MultiLossFn.apply(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights)
+    return MultiLossFn.apply(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights, soft_target,
+                             soft_kind, temperature, label_smoothing)
 
 
 __all__ = [n for n in dir() if not n.startswith('__')]      # everything, underscore helpers included: the package re-exports it (pylc_amd/ops/__init__.py)

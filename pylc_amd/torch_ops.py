@@ -463,6 +463,57 @@ def _mlw_bwd(ctx, dlosses, _dstats, _dbad):
 torch.library.register_autograd('pylc_hip::multiloss_weighted', _mlw_bwd, setup_context=_mlw_setup)
 
 
+# The same against a soft target (not in the reference): soft is float32 [B,C,H,W], read in place through its strides
+# -- soft_kind 'probs': a row q of C non-negative numbers per pixel, used as given (never renormalised); 'logits': teacher logits, q =
+# softmax(soft / temperature) taken in the kernel (only the teacher is softened).  pixel_weights may be None.  Returns (losses, stats,
+# bad): bad counts the rows with a negative, NaN or infinite entry and the bad weights; a row that sums to 0 is left out silently.  No
+# gradient flows into soft.
+@torch.library.custom_op('pylc_hip::multiloss_soft', mutates_args=())
+def multiloss_soft(logits: Tensor, soft: Tensor, soft_kind: str, temperature: float, pixel_weights: Optional[Tensor],
+                   class_weights: Optional[Tensor], w_ce: float, w_dice: float, w_focal: float) -> Tuple[Tensor, Tensor, Tensor]:
+    bad = torch.zeros(1, dtype=torch.int64, device=logits.device)
+    losses, saved = ops.multiloss_forward((True,), logits, None, class_weights, w_ce, w_dice, w_focal, None, None, bad, pixel_weights, soft,
+                                          soft_kind, temperature)[:2]
+    return losses, saved[2], bad
+
+
+@multiloss_soft.register_fake
+def _(logits, soft, soft_kind, temperature, pixel_weights, class_weights, w_ce, w_dice, w_focal):
+    return logits.new_empty(4), logits.new_empty(3 + 3 * logits.shape[1]), logits.new_empty(1, dtype=torch.int64)
+
+
+@torch.library.custom_op('pylc_hip::multiloss_soft_backward', mutates_args=())
+def multiloss_soft_backward(dlosses: Tensor, logits: Tensor, soft: Tensor, soft_kind: str, temperature: float, pixel_weights: Optional[Tensor],
+                            stats: Tensor, class_weights: Optional[Tensor], w_ce: float, w_dice: float, w_focal: float) -> Tensor:
+    if soft_kind not in ops.SOFT_KINDS:
+        raise L.PylcError("soft_kind is 'probs' or 'logits', got %r" % (soft_kind,))
+    inv_t = ops.soft_inv_temperature(temperature) if soft_kind == 'logits' else 1.0
+    state = ops.LossState((None, w_ce, w_dice, w_focal, None), None, (soft_kind, inv_t))
+    saved = (ops.as_nhwc(logits), soft, stats, class_weights) + (() if pixel_weights is None else (pixel_weights.contiguous(),))
+    return ops.multiloss_backward(state, saved, (True,), dlosses)[0]
+
+
+@multiloss_soft_backward.register_fake
+def _(dlosses, logits, soft, soft_kind, temperature, pixel_weights, stats, class_weights, w_ce, w_dice, w_focal):
+    return torch.empty_like(logits)
+
+
+def _mls_setup(ctx, inputs, output):
+    logits, soft, soft_kind, temperature, pw, cw, w_ce, w_dice, w_focal = inputs
+    ctx.save_for_backward(logits, soft, pw, output[1], cw)
+    ctx.w = (w_ce, w_dice, w_focal)
+    ctx.soft = (soft_kind, temperature)
+
+
+def _mls_bwd(ctx, dlosses, _dstats, _dbad):
+    logits, soft, pw, stats, cw = ctx.saved_tensors
+    return (torch.ops.pylc_hip.multiloss_soft_backward(dlosses, logits, soft, *ctx.soft, pw, stats, cw, *ctx.w), None, None, None, None, None,
+            None, None, None)
+
+
+torch.library.register_autograd('pylc_hip::multiloss_soft', _mls_bwd, setup_context=_mls_setup)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # input normalisation (Model.normalize_image, models/model.py:416-445, + the x3 channel stack :310-311) -> NHWC4 network input
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -479,4 +530,4 @@ def _(img, mean, std):
 REGISTERED = ('conv2d', 'conv2d_backward', 'dwconv3x3', 'dwconv3x3_backward', 'batch_norm_act', 'batch_norm_act_backward', 'relu',
               'relu_backward', 'max_pool2d', 'max_pool2d_backward', 'bilinear', 'bilinear_backward', 'global_avg_pool',
               'global_avg_pool_backward', 'dropout', 'multiloss', 'multiloss_backward', 'multiloss_ignore', 'multiloss_ignore_backward',
-              'image_pack', 'multiloss_weighted', 'multiloss_weighted_backward')
+              'image_pack', 'multiloss_soft', 'multiloss_soft_backward', 'multiloss_weighted', 'multiloss_weighted_backward')
