@@ -1008,6 +1008,44 @@ int pylc_multiloss_bwd_ls(const float* logits, int pitch, const void* target, in
                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Hard-pixel mining (csrc/mining.hip): a pixel-weight map for pylc_multiloss_*_w / _ls taken from the step's own
+ * logits -- the k pixels with the largest loss (bootstrapped / top-k cross-entropy) and / or every pixel whose loss is at least a cap
+ * (OHEM: true-class probability at most a threshold).  Not in the reference.
+ *
+ * Pixel n has the logits row z (NHWC, pitch >= C, C in 2..PYLC_MAX_CLASSES), a target t (uint8 or int64, judged as by _w: ignored, valid
+ * or bad; ignore_index INT32_MIN: none is ignored) and an optional weight u_n (the rules of _w).  nll_n = lse - z_t in float32 with the
+ * operation order of the loss head (zmax, sum expf(z - zmax) in ascending c, zmax + logf(sum)); a -0 counts as +0.  A CANDIDATE is a
+ * pixel that would take part in _w (valid target, 0 < u <= FLT_MAX) and whose nll is not NaN; +inf is a candidate.
+ *
+ * pylc_pixel_nll writes the float32 [N] map in one launch: nll at candidates and NaN rows, -1.0f at ignored pixels and pixels with
+ * u == 0, -2.0f at bad pixels (a bad target, or a bad weight on a valid target).
+ *
+ * pylc_hard_select selects from a map: with n_valid candidates, k = min(n_valid, max(min_kept, ceil(keep * n_valid))) (product and ceil
+ * in fp64, on the device); tau_k = the k-th largest candidate value (+inf for k == 0); tau = min(tau_k, nll_cap) (nll_cap = +inf: no
+ * cap; for a probability threshold pass -logf(thresh)).  In a map that is given, a value >= 0 (-0 included) under a weight that takes
+ * part is a candidate.  out[n] = u_n (1.0f without weights) at a candidate with nll >= tau -- every tie at tau is kept --, 0 at the
+ * other candidates, at -1.0f and under a weight of 0; everything else (-2.0f, NaN, another negative value, a negative / NaN / infinite
+ * weight) passes the input weight through unchanged (1.0f without weights), so that the loss that follows still counts a bad pixel and
+ * still goes NaN on a NaN row.  info: int64 [4] on the device, WRITTEN: n_valid, k, the number of kept pixels, the IEEE bits of tau
+ * (without a candidate: 0, 0, 0, the bits of +inf).  The selection is an exact radix select on the float bits with integer counts:
+ * bitwise reproducible, no sort, no host read.
+ *
+ * pylc_hard_pixel_weights is the two fused (the kernel that computes nll takes the first histogram; 4 launches and one memset): out and
+ * info are pylc_pixel_nll followed by pylc_hard_select bit for bit, nll_out (may be NULL) is pylc_pixel_nll's map bit for bit.
+ * workspace: pylc_mining_workspace_bytes(N) bytes, 16-byte aligned, contents undefined (it has room for the map when nll_out is NULL).
+ *
+ * PYLC_ERR_ARG, nothing launched: the argument errors of _w; N outside 1..2^31-1; keep outside [0, 1] or NaN; min_kept < 0; nll_cap NaN
+ * or < 0; keep == 0 with min_kept == 0 and nll_cap == +inf (nothing would be selected); a NULL or misaligned buffer. */
+size_t pylc_mining_workspace_bytes(long long N);
+int pylc_pixel_nll(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                   const float* pixel_weights, float* nll_out, void* stream);
+int pylc_hard_select(const float* nll, long long N, const float* pixel_weights, double keep, long long min_kept, float nll_cap,
+                     float* out, long long* info, void* workspace, void* stream);
+int pylc_hard_pixel_weights(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
+                            const float* pixel_weights, double keep, long long min_kept, float nll_cap, float* nll_out, float* out,
+                            long long* info, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Optimiser: torch.nn.utils.clip_grad_norm_(params, 0.5) models/model.py:326 + torch.optim.AdamW
  * models/model.py:240-245 over ONE flat fp32 arena holding every parameter.
  * ------------------------------------------------------------------------------------------- */

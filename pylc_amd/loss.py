@@ -10,7 +10,7 @@ from .runtime import runtime
 
 class MultiLoss(nn.Module):
     """MultiLoss(loss_weights={'weighted','weights','ce','dice','focal'}, schema={'n_classes','class_codes','class_labels'}, ignore_index=None,
-    label_smoothing=0.0).
+    label_smoothing=0.0, hard_mining=None).
 
     ignore_index (an int, not in the reference): pixels whose target equals it are left out of all three terms and get a zero gradient;
     targets may then be uint8 or int64.  Any other target outside 0..n_classes-1 is skipped too and counted in `.bad_targets` (an int64
@@ -30,15 +30,28 @@ class MultiLoss(nn.Module):
     in the kernel.  label_smoothing (0 <= eps < 1) smooths HARD targets in forward() only, q_c = (1 - eps) o_c + eps / C; ce_loss,
     dice_loss, focal_loss and all_losses -- the validation terms -- stay unsmoothed.
 
+    hard_mining (not in the reference): None, or {'keep':, 'min_kept':, 'thresh':} with every key optional and at
+    least one of keep (a fraction in (0, 1]: bootstrapped / top-k cross-entropy) and thresh (a probability in (0, 1): OHEM) present.  In
+    forward() only and on hard targets only, mining.hard_pixel_weights(pred, target, ...) -- computed from the detached logits and from the
+    pixel_weights that were passed -- takes the place of those pixel_weights, and the call goes on as forward(pred, target, mined_map) does;
+    label_smoothing applies as it does to any weighted call.  A pixel weight is one factor on EVERY term, so all three terms see the
+    mined map, Dice and Focal included: for mining on the cross-entropy alone set the other two loss weights to 0.  The pixels are ranked
+    by the plain -log p_t, not by the class-weighted loss.  ce_loss, dice_loss, focal_loss, all_losses and distill stay unmined; a soft
+    target together with hard_mining raises ValueError (the ranking needs a class index).  `.mined` holds the last call's info tensor
+    (int64 [4], device: candidates, k, kept pixels, the bits of the threshold).
+
     forward(pred, target) -> 0-d tensor (ce_w*CE + dice_w*Dice + focal_w*Focal) with grad; side effects
     .ce / .dsc / .fl hold the three terms (loss.py:107-112).  One kernel pass computes all three."""
 
-    def __init__(self, loss_weights, schema, ignore_index=None, label_smoothing=0.0):
+    def __init__(self, loss_weights, schema, ignore_index=None, label_smoothing=0.0, hard_mining=None):
         super().__init__()
         self.ignore_index = None if ignore_index is None else int(ignore_index)
         self.label_smoothing = float(label_smoothing)
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError('label_smoothing must lie in [0, 1), got %r' % (label_smoothing,))
+        from . import mining
+        self.hard_mining = mining.check_spec(hard_mining)
+        self.mined = None
         self.bad_targets = None
         self.n_classes = schema['n_classes']
         self.codes = schema.get('class_codes')
@@ -98,6 +111,13 @@ class MultiLoss(nn.Module):
                              soft_kind=kind, temperature=temperature)
 
     def forward(self, pred, target, pixel_weights=None):
+        if self.hard_mining is not None:
+            if torch.is_tensor(target) and target.dim() == 4 and target.is_floating_point():
+                raise ValueError('hard_mining ranks pixels by the loss of their class index: it cannot be combined with a soft target')
+            from . import mining
+            self._check(pred, target)
+            pixel_weights, self.mined = mining.hard_pixel_weights(pred, target, ignore_index=self.ignore_index, pixel_weights=pixel_weights,
+                                                                  **self.hard_mining)
         losses = self._all(pred, target, self.ce_weight, self.dsc_weight, self.fl_weight, pixel_weights, self.label_smoothing)
         self.ce, self.dsc, self.fl = losses[1].detach(), losses[2].detach(), losses[3].detach()
         return losses[0]

@@ -59,6 +59,10 @@ class Meta:
         #                                    5.20): what the inference keyword temperature='meta' divides the logits by
         self.label_smoothing = 0.0         # eps in [0, 1): training steps on hard targets run against (1 - eps) one_hot + eps / C;
         #                                    Model.eval stays unsmoothed.  0.0: the step as it was
+        self.hard_mining = None            # None, or {'keep':, 'min_kept':, 'thresh':} (keys optional): training steps on hard targets weigh the loss
+        #                                    by mining.hard_pixel_weights of their own logits -- the fraction `keep` of the pixels
+        #                                    with the largest loss and / or every pixel whose true-class probability is at most `thresh`;
+        #                                    Model.eval stays unmined.  None: the step as it was
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise AttributeError('unknown Meta field %r' % k)
@@ -202,7 +206,8 @@ class Model:
             loss_weights={'weighted': m.weighted, 'weights': m.weights, 'ce': m.ce_weight, 'dice': m.dice_weight,
                           'focal': m.focal_weight},
             schema={'n_classes': m.n_classes, 'class_codes': m.class_codes, 'class_labels': m.class_labels},
-            ignore_index=m.ignore_index, label_smoothing=getattr(m, 'label_smoothing', 0.0) or 0.0).to(self.device)
+            ignore_index=m.ignore_index, label_smoothing=getattr(m, 'label_smoothing', 0.0) or 0.0,
+            hard_mining=getattr(m, 'hard_mining', None)).to(self.device)
         ign = None if m.ignore_index is None else int(m.ignore_index)
         if self.scores is not None and self.scores.ignore_index != ign:
             self.scores.ignore_index, self.scores.counts = ign, None          # (the counts gain or lose the cell of the ignored pixels)
@@ -319,7 +324,8 @@ class Model:
     def train(self, x, y, pixel_weights=None, soft='probs', temperature=1.0):
         """One optimisation step (model.py:282-336).  pixel_weights (not in the reference): a float [B,H,W] map of the tiles' size, one
         weight per pixel of the loss (a confidence map, say); it is cropped like the target and multiplied into Meta.border_weight's map
-        where that is set.  Model.eval stays unweighted: validation losses remain comparable between runs.
+        where that is set.  Model.eval stays unweighted: validation losses remain comparable between runs.  With Meta.hard_mining that
+        product goes into the mining as its pixel_weights: a pixel of weight 0 is no candidate, and a kept pixel keeps its weight.
 
         A floating-point [B,C,H,W] y is a SOFT target, cropped on its last two dimensions for the U-Net and read in
         place: soft='probs', a row of C non-negative numbers per pixel, used as given (not renormalised; a row of zeros leaves the pixel
@@ -330,6 +336,8 @@ class Model:
         if soft_y:
             if soft not in ('probs', 'logits'):
                 raise ValueError("soft is 'probs' or 'logits', got %r" % (soft,))
+            if getattr(self.crit, 'hard_mining', None) is not None:
+                raise ValueError('Meta.hard_mining ranks pixels by the loss of their class index: it cannot be combined with a soft target')
             if soft == 'logits':
                 from .inference import resolve_temperature
                 resolve_temperature(self, temperature)                      # argument errors before any launch
@@ -429,6 +437,10 @@ class Model:
                                      'soft-target row with a negative, NaN or infinite entry' % (n_bad, self.meta.n_classes - 1))
                 raise ValueError('%d targets since the last report lie outside 0..%d and are not ignore_index=%d'
                                  % (n_bad, self.meta.n_classes - 1, self.meta.ignore_index))
+        mined = getattr(self.crit, 'mined', None)
+        if training and mined is not None:  # (the same place: the only host read of the mining, once per report interval)
+            n_valid, _, n_kept, _ = mined.tolist()
+            print('hard mining: kept %d / %d pixels of the last step' % (n_kept, n_valid))
         if self._best_by == 'iou' and self.scores is None:
             raise ValueError("best_by='iou' needs Model.scores (a metrics.ScoreLog)")
         if not training and self.scores is not None:

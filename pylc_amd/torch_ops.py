@@ -527,7 +527,31 @@ def _(img, mean, std):
     return img.new_empty((img.shape[0], 4, img.shape[2], img.shape[3]), dtype=torch.float32)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# hard-pixel mining (not in the reference; DESIGN.md section 5.22, pylc_amd/mining.py): the pixel-weight map of the k hardest pixels and /
+# or of every pixel whose true-class probability is at most thresh, from the logits themselves.  Returns (weights float32 [B,H,W], info
+# int64 [4]: n_valid, k, kept pixels, the bits of tau).  Neither output is differentiable: the map is a saved tensor of the loss operator
+# it is handed to (multiloss_weighted); the autograd registration only marks both outputs non-differentiable.
+# ------------------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op('pylc_hip::hard_pixel_weights', mutates_args=())
+def hard_pixel_weights(logits: Tensor, target: Tensor, pixel_weights: Optional[Tensor], keep: Optional[float], min_kept: int,
+                       thresh: Optional[float], ignore_index: Optional[int]) -> Tuple[Tensor, Tensor]:
+    from . import mining
+    return mining.hard_pixel_weights(logits, target, keep, min_kept, thresh, ignore_index, pixel_weights)
+
+
+@hard_pixel_weights.register_fake
+def _(logits, target, pixel_weights, keep, min_kept, thresh, ignore_index):
+    b, _, h, w = logits.shape
+    return logits.new_empty((b, h, w), dtype=torch.float32), logits.new_empty(4, dtype=torch.int64)
+
+
+torch.library.register_autograd('pylc_hip::hard_pixel_weights', lambda ctx, _dw, _dinfo: (None,) * 7,
+                                setup_context=lambda ctx, inputs, output: ctx.mark_non_differentiable(*output))
+
+
 REGISTERED = ('conv2d', 'conv2d_backward', 'dwconv3x3', 'dwconv3x3_backward', 'batch_norm_act', 'batch_norm_act_backward', 'relu',
               'relu_backward', 'max_pool2d', 'max_pool2d_backward', 'bilinear', 'bilinear_backward', 'global_avg_pool',
               'global_avg_pool_backward', 'dropout', 'multiloss', 'multiloss_backward', 'multiloss_ignore', 'multiloss_ignore_backward',
-              'image_pack', 'multiloss_soft', 'multiloss_soft_backward', 'multiloss_weighted', 'multiloss_weighted_backward')
+              'image_pack', 'hard_pixel_weights', 'multiloss_soft', 'multiloss_soft_backward', 'multiloss_weighted',
+              'multiloss_weighted_backward')
