@@ -1046,6 +1046,39 @@ int pylc_hard_pixel_weights(const float* logits, int pitch, const void* target, 
                             long long* info, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Edge-aware refinement of class probabilities: the guided filter (He, Sun, Tang, PAMI 2013) with a one-channel uint8 guide
+ * (csrc/refine.hip; no reference counterpart).  Omega(y,x) is the (2r+1)^2 window centred on (y,x) clipped to the image,
+ * n(y,x) its pixel count (r may exceed the image: the window is then the whole image).  All sums below run over Omega(y,x).
+ *
+ * pylc_luma_u8: planar uint8 [ch][H][W], ch 1 or 3 -> uint8 [H][W]: g = (77 R + 150 G + 29 B + 128) >> 8 in integers; a 1-channel image
+ * is copied.  No alignment is needed.
+ *
+ * pylc_guided_coeffs, stage 1, per class c of p (fp32, element (c,y,x) at p[c * plane_stride + y * row_pitch + x]: a window view of a
+ * larger volume is read in place; row_pitch >= W, plane_stride >= (H-1) * row_pitch + W), g uint8 [H][W] dense:
+ *   S_g = sum g, S_gg = sum g^2 (int32, exact), S_p = sum p_c, S_gp = sum g * p_c (fp32, each window summed from its own values, x
+ *   ascending within a row, then rows ascending), D = n * S_gg - S_g^2 (int64, exact);
+ *   D != 0:  var = D / (255^2 n^2), cov = (n S_gp - S_g S_p) / (255 n^2), a_c = cov / (var + eps), b_c = S_p / n - a_c * S_g / (255 n);
+ *   D == 0 (a flat window):  a_c = 0 exactly, b_c = S_p / n, whatever eps.
+ * a, b: fp32 [C][H][W] dense, written in full.  eps is in units of the guide scaled to [0, 1].  p is used as given: a non-finite value
+ * reaches the coefficients of every window that contains it.
+ *
+ * pylc_guided_apply, stage 2: q_c(y,x) = (sum a_c / n) * (g(y,x) / 255) + sum b_c / n; mask uint8 [H][W] = the first maximum of the raw
+ * q over c (np.argmax; a NaN at c > 0 never wins, as in pylc_blend_finalize); conf (may be NULL) fp32 [H][W] = that maximum clamped to
+ * [0, 1]; probs (may be NULL) fp32 [C][H][W] = q clamped to [0, 1] (clip = 1) or raw (clip = 0).  With probs == NULL no volume is
+ * written anywhere.  The raw q is linear in p and sums to 1 over c wherever p does; it can leave [0, 1] by a few hundredths at strong
+ * edges.  mask and conf are the same bytes with and without probs.
+ *
+ * No atomics: two runs give the same bytes.  C in 2..PYLC_MAX_CLASSES, r in 1..64, eps in [1e-6, 1].  Bytes per pixel: stage 1 reads
+ * 4 C + 1 and writes 8 C, stage 2 reads 8 C + 1 and writes 1 [+ 4] [+ 4 C] (plus the halo of a block's strip, served by the caches).
+ * PYLC_ERR_ARG, nothing launched: C, r, eps (NaN included), ch or clip out of range, H or W < 1, H * W >= 2^31, a row pitch below W, a
+ * plane stride below one plane, a NULL pointer other than probs / conf, an fp32 pointer that is not 4-byte aligned. */
+int pylc_luma_u8(const unsigned char* img, int ch, int H, int W, unsigned char* out, void* stream);
+int pylc_guided_coeffs(const float* p, long long plane_stride, long long row_pitch, const unsigned char* g, int C, int H, int W, int r,
+                       float eps, float* a, float* b, void* stream);
+int pylc_guided_apply(const float* a, const float* b, const unsigned char* g, int C, int H, int W, int r, int clip, unsigned char* mask,
+                      float* probs, float* conf, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Optimiser: torch.nn.utils.clip_grad_norm_(params, 0.5) models/model.py:326 + torch.optim.AdamW
  * models/model.py:240-245 over ONE flat fp32 arena holding every parameter.
  * ------------------------------------------------------------------------------------------- */

@@ -114,7 +114,7 @@ def _eval_mode(model):
 
 
 def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blend='reference', flip=False, return_probs=False,
-                  return_confidence=False, scales=None, scale_weights=None, temperature=None):
+                  return_confidence=False, scales=None, scale_weights=None, temperature=None, refine=None):
     """image: [C,H,W] raw 0..255, uint8 or float (host or device), fitted.  Returns the uint8 class mask [H,W] (device).
 
     group=None (default): LOCAL -- this process runs every tile and returns the mask, also inside a data-parallel job (a rank-0-only
@@ -130,6 +130,9 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blen
     (predict_blend_mean: the image at every scale, the probabilities resampled back and averaged with scale_weights); like flip it needs
     blend='mean'.  temperature (resolve_temperature: None, a positive float, or 'meta' for model.meta.temperature) divides the logits
     before every tile's softmax (pylc_blend_accumulate_t); like flip it needs blend='mean' and composes with flip and scales.
+    refine ({'radius': 8, 'eps': 1e-3}, pylc_amd.refine.check_spec) passes the mean probabilities through the guided filter with the uint8
+    image's luma as the guide (predict_blend_mean): the mask, probs and conf returned are the refined ones; like flip it
+    needs blend='mean'.
 
     A U-Net model (meta.arch == 'unet') takes predict_overlap_tile instead (any image size, stride default tile - 2*pad); its blend
     always was the mean, so `blend` is ignored and the other keywords pass through."""
@@ -137,13 +140,13 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blen
         raise ValueError("blend is 'reference' or 'mean', got %r" % (blend,))
     if model.meta.arch == 'unet':
         return predict_overlap_tile(model, image, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights,
-                                    temperature)
+                                    temperature, refine)
     if blend == 'mean':
         return predict_blend_mean(model, image, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights,
-                                  temperature)
+                                  temperature, refine)
     asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence),
                             ('scales', scales is not None), ('scale_weights', scale_weights is not None),
-                            ('temperature', temperature is not None)) if v]
+                            ('temperature', temperature is not None), ('refine', refine is not None)) if v]
     if asked:
         raise ValueError("%s needs blend='mean': the reference stitch mixes logits and probabilities, its scores are not probabilities"
                          % ', '.join(asked))
@@ -214,7 +217,7 @@ def overlap_tile_out(net, tile, pad):
 
 
 def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=None, return_probs=False, flip=False, return_confidence=False,
-                         scales=None, scale_weights=None, temperature=None):
+                         scales=None, scale_weights=None, temperature=None, refine=None):
     """Full-image U-Net inference by overlap tiles.  image: [C,H,W] raw 0..255, uint8 or float, host or device, any H, W >= out
     (out = tile - 2*meta.pad_size; no fitting).  stride in [1, out], default out.  Returns the uint8 class mask [H,W] (device), or
     (mask, probs) with probs the fp32 mean softmax probabilities [n_classes,H,W] when return_probs.
@@ -226,15 +229,15 @@ def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=Non
 
     flip=True (the mirrored windows as a second ensemble member), return_confidence=True (the tuple grows by conf, fp32 [H,W], the
     maximum probability) or scales (the multi-scale ensemble) move the call to the streaming accumulator, predict_blend_mean; without
-    them it is the one-launch stitch.  So does temperature (predict_image's keyword)."""
+    them it is the one-launch stitch.  So do temperature and refine (predict_image's keywords)."""
     if model.meta.arch != 'unet':
         raise ValueError('predict_overlap_tile needs a U-Net (meta.arch == "unet"), got %r' % model.meta.arch)
     L.init()
     pad = model.meta.pad_size
     out = overlap_tile_out(model.net, tile, pad)
-    if flip or return_confidence or scales is not None or scale_weights is not None or temperature is not None:
+    if flip or return_confidence or scales is not None or scale_weights is not None or temperature is not None or refine is not None:
         return predict_blend_mean(model, image, tile, out, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights,
-                                  temperature)
+                                  temperature, refine)
     stride = out if stride is None else int(stride)
     run = _TileRun(model, image, group)
     row_o, col_o = overlap_tile_grid(run.h, run.w, out, stride, pad)
@@ -347,7 +350,7 @@ def _blend_sweep(run, img, tile, out, stride, batch, members, beta=None):
 
 
 def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None, flip=False, return_probs=False, return_confidence=False,
-                       scales=None, scale_weights=None, temperature=None):
+                       scales=None, scale_weights=None, temperature=None, refine=None):
     """The streaming mean-probability blend (csrc/blend.hip) for a network that maps a `tile` window to its centred `out`
     square (DeepLab: out = tile; U-Net: out = tile - 2*pad).  image: [C,H,W] raw 0..255, uint8 or float, any H, W >= out; stride in
     [1, out], default tile // 2 for a same-size network and out otherwise.
@@ -374,8 +377,21 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
     geometry, so the step is linear -- and one all_reduce of the ensemble image runs at the end.
     temperature: None, a positive number T or 'meta' (resolve_temperature); with one, every tile's term is softmax(logits / T) through
     pylc_blend_accumulate_t, at every member and scale.  T = 1 gives the bytes of None.
+    refine: None, or a spec {'radius': 8, 'eps': 1e-3[, 'clip': True]} (pylc_amd.refine.check_spec; csrc/refine.hip).  With
+    one the finalizer is asked for the probability volume, and rank 0 passes it through refine.guided_refine with the luma of the image
+    the blend ran on (one pylc_luma_u8 launch) as the guide: mask, probs and conf are the refined ones, at every combination of flip,
+    scales and temperature.  The image must be uint8 (ValueError otherwise).  Memory: the filter's coefficients are two more volumes the
+    size of probs, 2 * 4 * C * H * W bytes -- 0.9 GB on a 3072 x 4096 photograph with 9 classes -- allocated after the accumulation
+    images above are done with.  None enters nothing new.
     Returns mask, or (mask[, probs][, conf])."""
     beta = resolve_temperature(model, temperature)                     # before any launch
+    spec = None
+    if refine is not None:
+        from . import refine as _refine
+        spec = _refine.check_spec(refine)
+        if not torch.is_tensor(image) or image.dtype != torch.uint8:
+            raise ValueError('refine needs a uint8 image (its luma is the guide), got %s'
+                             % (image.dtype if torch.is_tensor(image) else type(image).__name__))
     if stride is None:
         stride = tile // 2 if out == tile else out
     stride = int(stride)
@@ -404,9 +420,12 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
         dist.all_reduce(acc if plan is None else ens, group=group)
         if run.rank != 0:
             return None
-    if plan is None:
-        return _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence)
-    return _blend_finalize(ens, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, sum(p[3] for p in plan))
+    total = None if plan is None else sum(p[3] for p in plan)
+    if spec is None:
+        return _blend_finalize(acc if plan is None else ens, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, total)
+    _, probs = _blend_finalize(acc if plan is None else ens, cp, h, w, out, stride, ncls, members, True, False, total)
+    del acc, ens
+    return _refine.guided_refine(probs, img, spec[0], spec[1], return_probs, return_confidence, spec[2])
 
 
 def _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, total_weight=None):

@@ -247,6 +247,9 @@ SIGNATURES = {
     'pylc_pixel_nll': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P, _P]),
     'pylc_hard_select': (_I, [_P, _LL, _P, _D, _LL, _F, _P, _P, _P, _P]),
     'pylc_hard_pixel_weights': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _D, _LL, _F, _P, _P, _P, _P, _P]),
+    'pylc_luma_u8': (_I, [_P, _I, _I, _I, _P, _P]),
+    'pylc_guided_coeffs': (_I, [_P, _LL, _LL, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    'pylc_guided_apply': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     'pylc_sqnorm_workspace_floats': (_SZ, [_LL]),
     'pylc_grad_norm_clip': (_I, [_P, _LL, _F, _P, _P, _P]),
     'pylc_adamw_step': (_I, [_P, _P, _P, _P, _LL, _P, _F, _F, _F, _F, _F, _I, _P]),

@@ -188,7 +188,7 @@ def _sieve_result(res, pal, min_region, connectivity, fill, ignore_index):
 
 def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None, batch=8, group=None, return_probs=False, blend='reference',
                   flip=False, return_confidence=False, min_region=0, region_connectivity=4, region_fill='neighbour', ignore_index=None,
-                  scales=None, scale_weights=None, temperature=None):
+                  scales=None, scale_weights=None, temperature=None, refine=None):
     """A decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1] grayscale uint8, numpy or tensor) -> PhotoResult at the scaled size.
 
     DeepLab, blend='reference' (default): fit (stride default tile // 2, test.py:63), predict_image's sliding window on the uint8 fitted
@@ -202,6 +202,9 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     scales / scale_weights: the multi-scale ensemble of predict_blend_mean on the scaled-size image, every scale in
     [0.5, 2.0] relative to it; on a DeepLab it needs blend='mean', as flip does.  temperature (None, a positive number, or 'meta' for
     model.meta.temperature) divides the logits before every tile's softmax, under the same condition.
+    refine ({'radius': 8, 'eps': 1e-3}) passes the mean probabilities through the guided filter with the scaled-size
+    photograph's luma as the guide, under the same condition: mask, probs and confidence are the refined ones, and the order is refine ->
+    colourize / encode -> sieve.
 
     min_region > 1: regions of the final mask below that many pixels are sieved (regions.sieve with region_connectivity, region_fill and
     ignore_index; one pass), PhotoResult.rgb is recoloured from the sieved mask and PhotoResult.n_sieved counts the replaced pixels.  A
@@ -221,12 +224,15 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     if not unet and blend == 'reference':
         asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence),
                                 ('scales', scales is not None), ('scale_weights', scale_weights is not None),
-                                ('temperature', temperature is not None)) if v]
+                                ('temperature', temperature is not None), ('refine', refine is not None)) if v]
         if asked:
             raise ValueError("%s needs blend='mean' on a DeepLab: the reference sliding-window stitch mixes logits and probabilities, its "
                              "scores are not probabilities" % ', '.join(asked))
     from .inference import resolve_temperature
     resolve_temperature(model, temperature)          # argument errors before any launch
+    if refine is not None:
+        from .refine import check_spec
+        check_spec(refine)
     sieving = int(min_region) > 1
     if sieving:
         regions._check_mask(torch.empty((1, 1), dtype=torch.uint8), region_connectivity, ignore_index)
@@ -244,10 +250,10 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
         img = resize_area(_upload_photo(image, dev), h_s, w_s)      # at its own size: a relayout to [C,H,W]
         if unet:
             got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights,
-                                       temperature)
+                                       temperature, refine)
         else:
             got = predict_blend_mean(model, img, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales,
-                                     scale_weights, temperature)
+                                     scale_weights, temperature, refine)
         if got is None:
             return None
         got = list(got) if isinstance(got, tuple) else [got]
