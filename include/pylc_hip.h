@@ -1162,6 +1162,18 @@ int pylc_debug_wgrad_flags(int flags);
 /* Longest reduction, in K-steps of 32 pixels, of one block of a multi-tap wgrad (default 256; 0 = no cap, the round-3 plan): shorter
  * blocks start together round after round, so that the blocks sharing a pixel chunk stay within the L2's reach of each other. */
 int pylc_debug_wgrad_max_steps(int steps);
+/* Which kernel form the most recent dense conv launch (forward or data gradient) of this process took: a host-side value every launch site
+ * sets, so that a test can ASSERT the form a case was built to reach instead of restating the dispatch thresholds.  Changes no launch.
+ *   IGEMM         gather_gemm_kernel, any tile (fp32 operands; conv_igemm.hip)      PP      the 256 x 128 ping-pong kernel (fp32 operands)
+ *   STEM          the 7x7 / stride 2 thin-input patch kernel (conv_stem.hip)
+ *   PL128, PL128_NARROW, PL256    gg_pl_kernel on fp16-plane operands: 128-row tiles (wide / at most 64 stored channels), 256-row tiles
+ *   PLH, PLHN     the 3x3 halo kernels: 128-wide column tiles, eight waves / 64-wide column tiles, four waves
+ *   PLP           the persistent 1x1 kernel */
+enum {
+    PYLC_CONV_FORM_NONE = 0, PYLC_CONV_FORM_IGEMM = 1, PYLC_CONV_FORM_PP = 2, PYLC_CONV_FORM_STEM = 3, PYLC_CONV_FORM_PL128 = 4,
+    PYLC_CONV_FORM_PL128_NARROW = 5, PYLC_CONV_FORM_PL256 = 6, PYLC_CONV_FORM_PLH = 7, PYLC_CONV_FORM_PLHN = 8, PYLC_CONV_FORM_PLP = 9
+};
+int pylc_debug_last_conv_form(void);
 /* The next forward convs that take the ping-pong kernel record s_memtime stamps of block 0 (waves 0 and 4) at every
  * segment boundary into buf (2 x 256 uint64, device memory); NULL switches it off (tools/pp_stamps.py). */
 int pylc_debug_pp_stamps(unsigned long long* buf);

@@ -222,5 +222,7 @@ int conv_stem_init();
 extern int g_conv_precision;
 extern int g_wg_flags;
 extern int g_pp_flags;
+// pylc_debug_last_conv_form (include/pylc_hip.h PYLC_CONV_FORM_*): set by every gather-GEMM launch site, read by nothing in the library
+extern int g_last_conv_form;
 
 }  // namespace pylc

@@ -1528,6 +1528,7 @@ int g_pp_flags = 0;
 int g_wgrad_fast = 1;           // A/B knob (pylc_debug_pp_flags bit 8 clears it)
 unsigned long long* g_pp_stamps = nullptr;      // debug: see pylc_debug_pp_stamps
 int g_conv_precision = 2;      // 0 = fp32 MFMA, 1 = bf16x6, 2 = f16x3 (default); see pylc_set_conv_precision
+int g_last_conv_form = PYLC_CONV_FORM_NONE;      // which kernel form the most recent launch took (pylc_debug_last_conv_form)
 
 static thread_local int g_last_bm = 128;      // M-tile height of the most recent gather-GEMM launch on this thread
 
@@ -1535,6 +1536,7 @@ template <int BM, int BN, int WM, int WN, bool CIN4, int PREC>
 static int launch_gg(GatherGemmArgs& a, hipStream_t st) {
     PYLC_REQUIRE(a.w != nullptr, "conv: this geometry reads the fp32 filter, but only prepared planes were given");
     g_last_bm = BM;
+    g_last_conv_form = PYLC_CONV_FORM_IGEMM;
     const int tiles_m = cdiv(a.M, BM);
     a.tiles_n = cdiv(a.N_store, BN);
     const long long grid = (long long)tiles_m * a.tiles_n;
@@ -1555,6 +1557,7 @@ static bool takes_pp(const GatherGemmArgs& a) {
 
 static int launch_gg_pp(GatherGemmArgs& a, hipStream_t st) {
     g_last_bm = PP_BM;
+    g_last_conv_form = PYLC_CONV_FORM_PP;
     const int tiles_m = cdiv(a.M, PP_BM);
     a.tiles_n = cdiv(a.N_store, PP_BN);
     const long long n_tiles = (long long)tiles_m * a.tiles_n;
@@ -1719,6 +1722,9 @@ extern "C" int pylc_debug_pp_flags(int flags) { g_pp_flags = flags; g_wgrad_fast
 
 // tuning knob (tools/conv_bench.py): allow / forbid the 256x128 8-wave tile
 extern "C" int pylc_debug_set_big_tile(int on) { g_big_tile = on; return PYLC_OK; }
+
+// which kernel form the most recent conv launch took (a PYLC_CONV_FORM_* value): what a test asserts instead of restating the dispatch rules
+extern "C" int pylc_debug_last_conv_form(void) { return g_last_conv_form; }
 
 namespace {
 struct FwdEpilogue {

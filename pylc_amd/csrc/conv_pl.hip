@@ -2190,11 +2190,13 @@ bool takes_pl(const GatherGemmArgs& a) {
 template <int NTERMS, int BM>
 static void launch_pl(const GatherGemmArgs& a, unsigned grid, hipStream_t st) {
     constexpr int lds_bytes = pl_lds_bytes<NTERMS, BM>();
+    g_last_conv_form = BM == 256 ? PYLC_CONV_FORM_PL256 : PYLC_CONV_FORM_PL128;
     if (NTERMS == 3 && (a.dbg != nullptr || (a.dbg_flags & (64 | 128)))) {      // stamped / ablation build (tools/pl_stamps.py, pl_ablate.py)
         hipLaunchKernelGGL((gg_pl_kernel<3, BM, true>), dim3(grid), dim3(BM * 2), lds_bytes + 4096, st, a);
         return;
     }
     const bool ep = a.ep_scale != nullptr || a.ep_amax != nullptr || a.out_planes2 || a.ep_res != nullptr;      // fused inference epilogue
+    if (BM == 128 && a.N_store <= 64 && !(g_pp_flags & 65536) && a.bn_y == nullptr) g_last_conv_form = PYLC_CONV_FORM_PL128_NARROW;
     if (ep && a.N_store <= 64 && !(g_pp_flags & 65536)) hipLaunchKernelGGL((gg_pl_kernel<NTERMS, BM, false, false, true, true>), dim3(grid), dim3(BM * 2), lds_bytes, st, a);
     else if (ep) hipLaunchKernelGGL((gg_pl_kernel<NTERMS, BM, false, false, false, true>), dim3(grid), dim3(BM * 2), lds_bytes, st, a);
 #ifdef PYLC_EXPERIMENTAL
@@ -2252,6 +2254,7 @@ int launch_gg_pl(GatherGemmArgs& a, hipStream_t st) {
         a.n_tiles = (int)(halo_tiles_m * a.tiles_n);
         a.stagger = g_stagger >= 0 ? g_stagger : 0;          // (A/B knob pylc_debug_stagger, 2048-cycle units: 0 measured best -- profiles/r06_narrow_halo_ab.txt)
         a.stagger_blocks = 2 * kNumCU;
+        g_last_conv_form = PYLC_CONV_FORM_PLHN;
         if (ep_fused) {
             if (a.nterms == 1) hipLaunchKernelGGL((gg_plhn_kernel<1, true>), dim3((unsigned)a.n_tiles), dim3(256), plhn_lds_bytes<1>(), st, a);
             else hipLaunchKernelGGL((gg_plhn_kernel<3, true>), dim3((unsigned)a.n_tiles), dim3(256), plhn_lds_bytes<3>(), st, a);
@@ -2266,6 +2269,7 @@ int launch_gg_pl(GatherGemmArgs& a, hipStream_t st) {
         a.halo_tiles_m = (int)halo_tiles_m;
         const long long n_tiles = halo_tiles_m * a.tiles_n;
         a.n_tiles = (int)n_tiles;
+        g_last_conv_form = PYLC_CONV_FORM_PLH;
         if (a.ep_scale != nullptr || a.ep_amax != nullptr || a.out_planes2 || a.ep_res != nullptr) {
             if (a.nterms == 1) hipLaunchKernelGGL((gg_plh_kernel<1, false, true>), dim3((unsigned)n_tiles), dim3(512), plh_lds_bytes<1>(), st, a);
             else hipLaunchKernelGGL((gg_plh_kernel<3, false, true>), dim3((unsigned)n_tiles), dim3(512), plh_lds_bytes<3>(), st, a);
@@ -2314,6 +2318,7 @@ int launch_gg_pl(GatherGemmArgs& a, hipStream_t st) {
         (long long)a.M * a.y_pitch < (1ll << 31) && (a.add_mask == nullptr || (a.y_pitch == a.N_store && (reinterpret_cast<uintptr_t>(a.add_mask) & 7) == 0))) {
         const unsigned grid = (g_pp_flags & 1048576) ? (unsigned)n_tiles : ((g_pp_flags & 4194304) ? 3 * kNumCU : 2 * kNumCU);      // (bit 20: one tile per block -- the loop and epilogue code alone; bit 22: 768 blocks)
         const int epk = extra_src != nullptr ? (a.add_mask != nullptr ? 3 : 2) : (a.stats != nullptr ? 1 : 0);
+        g_last_conv_form = PYLC_CONV_FORM_PLP;
 #define PYLC_PLP(NT, E) hipLaunchKernelGGL((gg_plp_kernel<NT, E>), dim3(grid), dim3(256), plp_lds_bytes<NT>(), st, a)
         if (a.dbg != nullptr && epk <= 1) {          // stamped build (tools/plp_stamps.py)
             if (epk == 0) hipLaunchKernelGGL((gg_plp_kernel<3, 0, true>), dim3(grid), dim3(256), plp_lds_bytes<3>() + 4096, st, a);

@@ -229,6 +229,7 @@ int launch_stem_fwd(GatherGemmArgs& g, hipStream_t st) {
     a.patches_per_image = (g.P / ST_PH) * a.patches_w;
     a.n_patches = a.B * a.patches_per_image;
     g.halo_tiles_m = a.n_patches;                            // rows of the statistics partial (conv2d_fwd_impl reports it)
+    g_last_conv_form = PYLC_CONV_FORM_STEM;
     const int grid = a.n_patches < kNumCU ? a.n_patches : kNumCU;
     hipLaunchKernelGGL(stem_fwd_kernel, dim3((unsigned)grid), dim3(ST_THR), ST_LDS, st, a);
     PYLC_LAUNCH_CHECK();

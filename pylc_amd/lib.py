@@ -108,6 +108,7 @@ SIGNATURES = {
     'pylc_debug_wgrad_m16': (_I, [_I]),
     'pylc_debug_wgrad_dma': (_I, [_I]),
     'pylc_debug_pp_stamps': (_I, [_P]),
+    'pylc_debug_last_conv_form': (_I, []),
     'pylc_amax': (_I, [_P, _LL, _I, _I, _P, _P]),
     'pylc_amax_segments': (_I, [_P, _P, _I, _P, _P]),
     'pylc_to_planes': (_I, [_P, _I, _P, _I, _LL, _LL, _I, _P, _I, _P]),
@@ -291,6 +292,9 @@ def _load():
 lib = _load()
 _initialised = False
 
+# PYLC_CONV_FORM_* (include/pylc_hip.h): what pylc_debug_last_conv_form returns, by name
+CONV_FORMS = ('none', 'igemm', 'pp', 'stem', 'pl128', 'pl128-narrow', 'pl256', 'plh', 'plhn', 'plp')
+
 
 def check(rc):
     if rc != 0:
@@ -321,7 +325,7 @@ def init():
         for item in filter(None, (t.strip() for t in os.environ.get('PYLC_DEBUG_KNOBS', '').split(','))):
             name, _, val = item.partition('=')
             fn = getattr(lib, 'pylc_debug_' + name, None)
-            if fn is None or name in ('pp_stamps',):
+            if fn is None or name in ('pp_stamps', 'last_conv_form'):
                 raise PylcError('PYLC_DEBUG_KNOBS: no knob %r' % name)
             fn(int(val))
         _initialised = True

@@ -34,7 +34,7 @@ def mode(request, dev):
 CASES = [
     (256, 1024, 1, 1, 0, 1, 2, 32, 32, 'planes', True),      # bottleneck conv3 + identity residual (resnet.py:47-51)
     (1024, 256, 1, 1, 0, 1, 2, 32, 32, 'none', True),        # conv1
-    (256, 256, 3, 1, 1, 1, 2, 32, 32, 'none', True),         # conv2: the halo kernel
+    (256, 256, 3, 1, 1, 1, 2, 32, 32, 'none', True),         # conv2: 8 patches, too few for the halo kernels -- the 128-row multi-tap kernel (pl128)
     (64, 64, 3, 1, 1, 1, 2, 48, 48, 'none', True),           # layer1 3x3: narrow wave layout
     (256, 64, 1, 1, 0, 1, 2, 40, 36, 'fp32', False),         # narrow 1x1, ragged M, fp32 residual, no ReLU
     (128, 128, 3, 2, 1, 1, 2, 45, 45, 'none', True),         # stride 2
@@ -91,14 +91,14 @@ def test_fused_inference_conv_on_planes(dev, mode, case, out_planes):
 # cin, cout, k, pad, B, H, W, residual as planes, relu
 LEAN_EP_CASES = [
     (256, 1024, 1, 0, 4, 32, 32, True, True),        # bottleneck conv3 + identity residual: whole-line residual loads and stores
-    (1024, 256, 1, 0, 4, 32, 32, False, True),       # conv1, the 256-row kernel's shapes
-    (256, 256, 3, 1, 4, 32, 32, False, True),        # conv2: the halo kernel
+    (1024, 256, 1, 0, 4, 32, 32, False, True),       # conv1: a long reduction, but 32 tiles of 256 rows where that kernel needs 256 -- 128-row tiles (pl128)
+    (256, 256, 3, 1, 4, 32, 32, False, True),        # conv2: 16 patches, too few for the halo kernels -- the 128-row multi-tap kernel (pl128)
     (64, 64, 3, 1, 2, 64, 64, False, True),          # layer1 3x3, narrow wave layout
     (64, 64, 3, 1, 8, 128, 128, False, True),        # ... on the halo kernel's narrow form
     (256, 64, 1, 0, 2, 64, 64, False, False),        # narrow 1x1, no ReLU
     (128, 512, 1, 0, 2, 40, 36, True, False),        # ragged M: the last tile takes the general path, the others the lean one
     (512, 96, 1, 0, 2, 32, 32, True, True),          # Cout = 96: the second wave column is half outside -> general path beside lean waves
-    (128, 128, 3, 0, 2, 68, 68, False, True, True),  # the U-Net's valid 3x3 conv WITH a bias (unet.py:111): 66 x 66 outputs, ragged halo patches
+    (128, 128, 3, 0, 2, 68, 68, False, True, True),  # the U-Net's valid 3x3 conv WITH a bias (unet.py:111): 66 x 66 outputs, too ragged for the halo kernels (50 patches cover 1.47 x the pixels) -- pl128
     (64, 128, 1, 0, 2, 64, 64, False, True, True),   # bias on the 1x1 kernels
     (256, 1024, 1, 0, 32, 32, 32, True, True),       # BASELINE size: configs[2]'s conv3 at batch 32 (2048 tiles, four rounds of blocks)
     (728, 728, 1, 0, 8, 64, 64, True, True, True),   # BASELINE size: configs[4]'s middle-flow pointwise conv at 1024^2 / 16, batch 8

@@ -41,7 +41,8 @@ CONV_CASES = [
     (128, 64, 3, 1, 0, 1, 1, 20, 20, True),
     (728, 728, 1, 1, 0, 1, 1, 8, 8, False),       # Xception pointwise (Cin % 32 != 0)
     (32, 2048, 1, 1, 0, 1, 4, 1, 1, False),       # ASPP image-pool branch: 1x1 spatial
-    # >= 192 tiles of 256x128: these dispatch to the 8-wave 256x128 tile (fwd and dgrad)
+    # >= 192 tiles of 256x128 (the fp32-operand dispatch): in f16x3 the ping-pong kernel (fwd; dgrad too except the Cin = 72 case), in bf16x6 the
+    # 8-wave 256x128 tile, in the fp32-MFMA mode 128x128 tiles (what pylc_debug_last_conv_form reports: pp / igemm)
     (128, 128, 3, 1, 1, 1, 4, 112, 112, False),
     (72, 256, 3, 1, 12, 12, 8, 64, 64, False),    # atrous with tap skipping, Cin % 16 != 0
     (256, 256, 1, 1, 0, 1, 8, 64, 64, True),
