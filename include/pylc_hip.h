@@ -741,6 +741,36 @@ int pylc_ensemble_finalize(const float* ens, int pitch, int H, int W, int C, flo
                            float* conf, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The window-weighted blend (csrc/blend.hip, csrc/multiscale.hip): a tile's softmax counts
+ * w_t(y, x) = win[y - oy_t] * win[x - ox_t] times, win one fp32 device table of `out` positive floats used along both axes and
+ * indexed by the pixel's position inside the placed tile (for a flip member: after the mirrored logits are mirrored back, so
+ * the divisor does not depend on the member).  p = sum_t w_t * softmax_t / sum_t w_t; the divisor is separable,
+ * members * sum_y[y] * sum_x[x], and is read from two per-axis tables instead of a weight image.  A table of ones gives the
+ * bytes of the plain entry points above.  The entry points cannot inspect a device table and do not try: a zero (or a
+ * negative or non-finite) entry gives NaN / inf probabilities, not a fault -- pylc_amd.inference.blend_window validates.
+ * Arguments are checked on the host (PYLC_ERR_ARG, nothing is launched); nothing is allocated.
+ * ------------------------------------------------------------------------------------------- */
+/* pylc_blend_accumulate_t's gather with the weight: wt = win[ly] * win[lx] (one fp32 product), then
+ * acc[y][x][c] += wt * (the plain term); covering tiles in ascending index; inv_temperature = 1.0f is the plain softmax,
+ * exactly.  Same argument checks as pylc_blend_accumulate_t; win non-NULL and 4-B aligned.  A pixel of the batch's box that no
+ * tile of the batch covers is not written; channels C .. acc_pitch-1 are left alone. */
+int pylc_blend_accumulate_w(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
+                            int flip, float* acc, int acc_pitch, const float* win, float inv_temperature, void* stream);
+/* One axis of length n (>= out; 1 <= stride <= out): sums[y] = the fp32 sum of win[y - o_i] over the tiles i that cover y, the
+ * unclamped tiles in ascending order, then the clamped last tile.  sums: fp32 [n], 4-B aligned, distinct from win.  Called
+ * once per axis and image size. */
+int pylc_blend_window_sums(const float* win, int out, int stride, int n, float* sums, void* stream);
+/* pylc_blend_finalize with the divisor (float)members * (sum_y[y] * sum_x[x]) (sum_y fp32 [H], sum_x fp32 [W], 4-B aligned);
+ * p[c] = acc[c] / that, a true fp32 division; mask, probs and conf as pylc_blend_finalize writes them. */
+int pylc_blend_finalize_w(const float* acc, int acc_pitch, int H, int W, int C, int members, const float* sum_y, const float* sum_x,
+                          unsigned char* mask, float* probs, float* conf, void* stream);
+/* pylc_blend_resample_accumulate with the four corner divisors (float)members * (sum_y_s[.] * sum_x_s[.]) read from the scaled
+ * size's tables (fp32 [Hs] and [Ws], 4-B aligned); everything else operation for operation.  Hs, Ws >= 1. */
+int pylc_blend_resample_accumulate_w(const float* acc_s, int src_pitch, int Hs, int Ws, int members, float weight, int C,
+                                     const float* sum_y_s, const float* sum_x_s, float* ens, int ens_pitch, int H, int W, int add,
+                                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training tile sets (csrc/dataset.hip): the reference's `pylc.py extract` (Extractor.extract -> __split,
  * utils/extract.py:106-231, 279-310) and the sums its dataset profile is made of (utils/profile.py:92-150).
  * Integer arithmetic only: the results are exact and independent of band_rows and of first_tile chunking.

@@ -12,6 +12,12 @@
 //                               class = first maximum; mask (four pixels per lane, one dword), optional probs [C][H][W], conf [H][W].
 //                               (blend_finalize.h: multiscale.hip's ensemble finalizer is the same body with one divisor.)
 //
+// The window-weighted blend: a tile's term counts wt = win[ly] * win[lx] times, win one table of `out` floats.
+//   blend_accumulate_kernel<C, 1, const float*>  the same gather, acc[c] += wt * (softmax term); the same bytes moved, plus the 4 * out B table.
+//   blend_window_sums_kernel      one axis' sums of win over the covering tiles: a table of n floats, the separable form of the divisor.
+//   blend_finalize_kernel<C, 0, BlendTableDiv>  the same finalizer body, p[c] = acc[c] / (members * (sum_y[y] * sum_x[x])).
+// A table of ones gives the plain kernels' bytes: every product and sum is then an exact small integer.
+//
 // The geometry is overlap_geom.h's: o_i = min(i*stride, n - out); the fitted sliding-window grid of stitch.hip is the case out = tile
 // in which the clamp is never active.  Bandwidth kernels: no LDS, no MFMA.
 #include "blend_finalize.h"
@@ -25,10 +31,14 @@ namespace {
 // the pixels [y0, y0 + bh) x [x0, x0 + bw) that the tiles first .. first + count - 1 can touch
 struct BlendBox { int y0, x0, bh, bw; };
 
-// TEMP: the tile's term is softmax(beta * logits) (pylc_blend_accumulate_t); without it `beta` is not read
-template <int C, bool TEMP>
+// TEMP: the tile's term is softmax(beta * logits) (pylc_blend_accumulate_t); without it `beta` is not read.
+// Win (none, or one const float* after beta; TEMP): the window table of pylc_blend_accumulate_w -- the term is multiplied by
+// wt = win[ly] * win[lx], ly and lx the pixel's position inside the placed tile (for the flip member: after the mirrored logits are
+// mirrored back).  Without one the parameter list and the code are the plain forms'.
+template <int C, bool TEMP, class... Win>
 __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __restrict__ logits, BlendGeom g, BlendBox box, int first, int count,
-                                                                int flip, float* __restrict__ acc, float beta) {
+                                                                int flip, float* __restrict__ acc, float beta, Win... win) {
+    static_assert(sizeof...(Win) <= 1 && !(!TEMP && sizeof...(Win)), "the windowed gather is the temperature form with one table");
     constexpr int NV = (C + 3) / 4;
     const long long total = (long long)box.bh * box.bw;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -55,9 +65,12 @@ __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __re
                     loaded = true;
                 }
                 int lx = x - overlap_origin(tj, g.W, g.out, g.stride);
+                [[maybe_unused]] float wt = 1.f;
+                if constexpr (sizeof...(Win) == 1) wt = ((win[ly] * win[lx]), ...);        // the placed position: before the read's flip mapping
                 lx = flip ? g.out - 1 - lx : lx;
                 const ot_f32x4* src = reinterpret_cast<const ot_f32x4*>(logits + (((size_t)k * g.out + ly) * g.out + lx) * g.pitch);
-                if constexpr (TEMP) softmax_add<C, NV * 4, true>(src, a, beta);
+                if constexpr (sizeof...(Win) == 1) softmax_add<C, NV * 4, true, true>(src, a, beta, wt);
+                else if constexpr (TEMP) softmax_add<C, NV * 4, true>(src, a, beta);
                 else softmax_add<C>(src, a);         // stitch_overlap_kernel's term, operation for operation
             }
         }
@@ -72,14 +85,30 @@ __global__ __launch_bounds__(256) void blend_accumulate_kernel(const float* __re
     }
 }
 
+// sums[y] = the fp32 sum of win[y - o_i] over the tiles i covering coordinate y of an axis of length n, in overlap_cover's visiting
+// order (the unclamped tiles ascending, then the clamped last tile); one lane per coordinate.
+__global__ __launch_bounds__(256) void blend_window_sums_kernel(const float* __restrict__ win, int n, int out, int stride, int cnt,
+                                                                 float* __restrict__ sums) {
+    const int y = blockIdx.x * blockDim.x + threadIdx.x;
+    if (y >= n) return;
+    const Cover c = overlap_cover(y, n, out, stride, cnt);
+    float s = 0.f;
+    for (int ia = c.lo; ia <= c.hi + c.last; ++ia) {
+        const int ti = ia <= c.hi ? ia : cnt - 1;
+        s += win[y - overlap_origin(ti, n, out, stride)];
+    }
+    sums[y] = s;
+}
+
 }  // namespace
 }  // namespace pylc
 
 using namespace pylc;
 
+// win: NULL for the plain forms, else the window table [out] of pylc_blend_accumulate_w (TEMP then holds)
 template <bool TEMP>
 static int blend_accumulate_impl(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
-                                 int flip, float* acc, int acc_pitch, void* stream, float beta) {
+                                 int flip, float* acc, int acc_pitch, void* stream, float beta, const float* win = nullptr) {
     PYLC_REQUIRE(logits && pitch >= C && pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0,
                  "blend_accumulate: logits must be 16-B aligned NHWC tiles with a pitch >= C, multiple of 4");
     PYLC_REQUIRE(acc && acc_pitch >= C && acc_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(acc) & 15) == 0,
@@ -106,7 +135,16 @@ static int blend_accumulate_impl(const float* logits, int pitch, int first_tile,
     const int blocks = ot_grid((long long)box.bh * box.bw);
     hipStream_t st = as_stream(stream);
 #define LAUNCH_BA(CC) hipLaunchKernelGGL((blend_accumulate_kernel<CC, TEMP>), dim3(blocks), dim3(256), 0, st, logits, g, box, first_tile, n_tiles, flip, acc, beta)
+#define LAUNCH_BW(CC) hipLaunchKernelGGL((blend_accumulate_kernel<CC, true, const float*>), dim3(blocks), dim3(256), 0, st, logits, g, box, first_tile, n_tiles, flip, acc, beta, win)
+    if constexpr (TEMP) {
+        if (win != nullptr) {
+            PYLC_FOR_CLASSES(C, LAUNCH_BW, "blend_accumulate")
+            PYLC_LAUNCH_CHECK();
+            return PYLC_OK;
+        }
+    }
     PYLC_FOR_CLASSES(C, LAUNCH_BA, "blend_accumulate")
+#undef LAUNCH_BW
 #undef LAUNCH_BA
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
@@ -121,6 +159,45 @@ extern "C" int pylc_blend_accumulate_t(const float* logits, int pitch, int first
                                        int flip, float* acc, int acc_pitch, void* stream, float inv_temperature) {
     PYLC_REQUIRE(inv_temperature > 0.f && inv_temperature <= 3.4028234e38f, "blend_accumulate_t: inv_temperature must be positive and finite");
     return blend_accumulate_impl<true>(logits, pitch, first_tile, n_tiles, H, W, out, stride, C, flip, acc, acc_pitch, stream, inv_temperature);
+}
+
+extern "C" int pylc_blend_accumulate_w(const float* logits, int pitch, int first_tile, int n_tiles, int H, int W, int out, int stride, int C,
+                                       int flip, float* acc, int acc_pitch, const float* win, float inv_temperature, void* stream) {
+    PYLC_REQUIRE(win && (reinterpret_cast<uintptr_t>(win) & 3) == 0, "blend_accumulate_w: win must be a 4-B aligned table of `out` floats");
+    PYLC_REQUIRE(inv_temperature > 0.f && inv_temperature <= 3.4028234e38f, "blend_accumulate_w: inv_temperature must be positive and finite");
+    return blend_accumulate_impl<true>(logits, pitch, first_tile, n_tiles, H, W, out, stride, C, flip, acc, acc_pitch, stream, inv_temperature, win);
+}
+
+extern "C" int pylc_blend_window_sums(const float* win, int out, int stride, int n, float* sums, void* stream) {
+    PYLC_REQUIRE(win && sums, "blend_window_sums: NULL pointer");
+    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(win) & 3) == 0 && (reinterpret_cast<uintptr_t>(sums) & 3) == 0,
+                 "blend_window_sums: win and sums must be 4-B aligned");
+    PYLC_REQUIRE(static_cast<const float*>(sums) != win, "blend_window_sums: sums may not alias win");
+    if (int rc = overlap_check("blend_window_sums", n, n, out, stride, 0)) return rc;
+    hipLaunchKernelGGL(blend_window_sums_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), win, n, out, stride,
+                       overlap_count(n, out, stride), sums);
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_blend_finalize_w(const float* acc, int acc_pitch, int H, int W, int C, int members, const float* sum_y, const float* sum_x,
+                                     unsigned char* mask, float* probs, float* conf, void* stream) {
+    PYLC_REQUIRE(acc && mask && acc_pitch >= C && acc_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(acc) & 15) == 0,
+                 "blend_finalize_w: acc must be a 16-B aligned [H][W][acc_pitch] image with acc_pitch >= C, multiple of 4");
+    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 3) == 0, "blend_finalize_w: mask must be 4-B aligned");
+    PYLC_REQUIRE(sum_y && sum_x && (reinterpret_cast<uintptr_t>(sum_y) & 3) == 0 && (reinterpret_cast<uintptr_t>(sum_x) & 3) == 0,
+                 "blend_finalize_w: sum_y [H] and sum_x [W] must be 4-B aligned tables");
+    PYLC_REQUIRE(members >= 1, "blend_finalize_w: members=%d", members);
+    PYLC_REQUIRE(H >= 1 && W >= 1, "blend_finalize_w: H=%d W=%d", H, W);
+    const BlendGeom g{H, W, 0, 0, 0, 0, 0, acc_pitch};
+    const BlendTableDiv div{sum_y, sum_x};
+    const int blocks = ot_grid(cdiv<long long>((long long)H * W, kOtPx));
+    hipStream_t st = as_stream(stream);
+#define LAUNCH_FW(CC) hipLaunchKernelGGL((blend_finalize_kernel<CC, false, BlendTableDiv>), dim3(blocks), dim3(256), 0, st, acc, g, 1, (float)members, mask, probs, conf, div)
+    PYLC_FOR_CLASSES(C, LAUNCH_FW, "blend_finalize_w")
+#undef LAUNCH_FW
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
 }
 
 extern "C" int pylc_blend_finalize(const float* acc, int acc_pitch, int H, int W, int out, int stride, int C, int members, unsigned char* mask,

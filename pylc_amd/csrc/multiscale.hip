@@ -7,6 +7,7 @@
 //                                tiles) at the four source pixels: blend_finalize_kernel's division, the count from the scaled image's
 //                                geometry.  One destination pixel per lane, lanes along x, 16-byte loads of the four source vectors, the
 //                                destination vector loaded (add) and stored once; channels C .. ens_pitch-1 are not written.
+//   blend_resample_kernel<C, BlendTableDiv>  the same body with the four corner divisors read from the scaled size's window sums.
 //   blend_finalize_kernel<C, false> (blend_finalize.h)   p = ens / total_weight, mask, probs, conf as pylc_blend_finalize writes them.
 //
 // The coordinate rule, per axis (destination length n, source length ns): s = (i + 0.5) * ((double)ns / n) - 0.5 in double, clamped to
@@ -73,17 +74,28 @@ __device__ __forceinline__ int cover_count(int y, int n, int out, int stride, in
 
 // The channels are walked four at a time: the four corners' 16-byte loads of one quad, its 4 results, the destination's quad.  Every
 // 16-byte piece of the five vectors is touched once, and no more than one quad of each is live at a time.
-template <int C>
-__global__ __launch_bounds__(256) void blend_resample_kernel(const float* __restrict__ acc, ResampleGeom g, float* __restrict__ ens) {
+// Tab (none, or one BlendTableDiv after ens): pylc_blend_resample_accumulate_w -- the four corner divisors are
+// members * (sum_y[.] * sum_x[.]) from the scaled size's window sums; g.out, g.stride, g.rows and g.cols are then not read.  Without
+// one the parameter list and the code are the plain form's.
+template <int C, class... Tab>
+__global__ __launch_bounds__(256) void blend_resample_kernel(const float* __restrict__ acc, ResampleGeom g, float* __restrict__ ens, Tab... tab) {
+    static_assert(sizeof...(Tab) <= 1, "one table divisor at most");
     constexpr int NV = (C + 3) / 4;
     const long long total = (long long)g.H * g.W;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int y = (int)(i / g.W), x = (int)(i - (long long)y * g.W);
         const Axis ay = bilinear_axis(y, g.ry, g.Hs), ax = bilinear_axis(x, g.rx, g.Ws);
-        const int ny0 = cover_count(ay.i0, g.Hs, g.out, g.stride, g.rows), ny1 = cover_count(ay.i1, g.Hs, g.out, g.stride, g.rows);
-        const int nx0 = cover_count(ax.i0, g.Ws, g.out, g.stride, g.cols), nx1 = cover_count(ax.i1, g.Ws, g.out, g.stride, g.cols);
-        const float n00 = (float)(g.members * ny0 * nx0), n01 = (float)(g.members * ny0 * nx1);
-        const float n10 = (float)(g.members * ny1 * nx0), n11 = (float)(g.members * ny1 * nx1);
+        float n00, n01, n10, n11;
+        if constexpr (sizeof...(Tab) == 1) {
+            const float fm = (float)g.members;
+            n00 = fm * (tab(ay.i0, ax.i0), ...); n01 = fm * (tab(ay.i0, ax.i1), ...);
+            n10 = fm * (tab(ay.i1, ax.i0), ...); n11 = fm * (tab(ay.i1, ax.i1), ...);
+        } else {
+            const int ny0 = cover_count(ay.i0, g.Hs, g.out, g.stride, g.rows), ny1 = cover_count(ay.i1, g.Hs, g.out, g.stride, g.rows);
+            const int nx0 = cover_count(ax.i0, g.Ws, g.out, g.stride, g.cols), nx1 = cover_count(ax.i1, g.Ws, g.out, g.stride, g.cols);
+            n00 = (float)(g.members * ny0 * nx0); n01 = (float)(g.members * ny0 * nx1);
+            n10 = (float)(g.members * ny1 * nx0); n11 = (float)(g.members * ny1 * nx1);
+        }
         const ot_f32x4* s00 = reinterpret_cast<const ot_f32x4*>(acc + ((size_t)ay.i0 * g.Ws + ax.i0) * g.src_pitch);
         const ot_f32x4* s01 = reinterpret_cast<const ot_f32x4*>(acc + ((size_t)ay.i0 * g.Ws + ax.i1) * g.src_pitch);
         const ot_f32x4* s10 = reinterpret_cast<const ot_f32x4*>(acc + ((size_t)ay.i1 * g.Ws + ax.i0) * g.src_pitch);
@@ -159,6 +171,35 @@ extern "C" int pylc_blend_resample_accumulate(const float* acc_s, int src_pitch,
 #define LAUNCH_RS(CC) hipLaunchKernelGGL((blend_resample_kernel<CC>), dim3(blocks), dim3(256), 0, st, acc_s, g, ens)
     PYLC_FOR_CLASSES(C, LAUNCH_RS, "blend_resample_accumulate")
 #undef LAUNCH_RS
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+extern "C" int pylc_blend_resample_accumulate_w(const float* acc_s, int src_pitch, int Hs, int Ws, int members, float weight, int C,
+                                                const float* sum_y_s, const float* sum_x_s, float* ens, int ens_pitch, int H, int W, int add,
+                                                void* stream) {
+    PYLC_REQUIRE(acc_s && ens, "blend_resample_accumulate_w: NULL pointer");
+    PYLC_REQUIRE(src_pitch >= C && src_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(acc_s) & 15) == 0,
+                 "blend_resample_accumulate_w: acc_s must be a 16-B aligned [Hs][Ws][src_pitch] image with src_pitch >= C, multiple of 4");
+    PYLC_REQUIRE(ens_pitch >= C && ens_pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(ens) & 15) == 0,
+                 "blend_resample_accumulate_w: ens must be a 16-B aligned [H][W][ens_pitch] image with ens_pitch >= C, multiple of 4");
+    PYLC_REQUIRE(static_cast<const float*>(ens) != acc_s, "blend_resample_accumulate_w: ens may not alias acc_s");
+    PYLC_REQUIRE(sum_y_s && sum_x_s && (reinterpret_cast<uintptr_t>(sum_y_s) & 3) == 0 && (reinterpret_cast<uintptr_t>(sum_x_s) & 3) == 0,
+                 "blend_resample_accumulate_w: sum_y_s [Hs] and sum_x_s [Ws] must be 4-B aligned tables");
+    PYLC_REQUIRE(members >= 1, "blend_resample_accumulate_w: members=%d", members);
+    PYLC_REQUIRE(weight > 0.f && weight <= 3.4e38f, "blend_resample_accumulate_w: weight %g must be positive and finite", (double)weight);
+    PYLC_REQUIRE(Hs >= 1 && Ws >= 1, "blend_resample_accumulate_w: Hs=%d Ws=%d", Hs, Ws);
+    PYLC_REQUIRE(H >= 1 && W >= 1 && (add == 0 || add == 1), "blend_resample_accumulate_w: H=%d W=%d add=%d", H, W, add);
+    ResampleGeom g;
+    g.Hs = Hs; g.Ws = Ws; g.out = 0; g.stride = 0; g.rows = 0; g.cols = 0;
+    g.src_pitch = src_pitch; g.H = H; g.W = W; g.ens_pitch = ens_pitch; g.members = members; g.add = add;
+    g.ry = (double)Hs / H; g.rx = (double)Ws / W; g.weight = weight;
+    const BlendTableDiv tab{sum_y_s, sum_x_s};
+    const int blocks = ot_grid((long long)H * W);
+    hipStream_t st = as_stream(stream);
+#define LAUNCH_RW(CC) hipLaunchKernelGGL((blend_resample_kernel<CC, BlendTableDiv>), dim3(blocks), dim3(256), 0, st, acc_s, g, ens, tab)
+    PYLC_FOR_CLASSES(C, LAUNCH_RW, "blend_resample_accumulate_w")
+#undef LAUNCH_RW
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
 }

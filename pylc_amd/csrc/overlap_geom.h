@@ -37,8 +37,10 @@ __device__ __forceinline__ Cover overlap_cover(int y, int n, int out, int stride
 // mean-probability blend, stated once so that the one-shot and the streaming blend add the same bits in the same order.
 // TEMP (pylc_blend_accumulate_t): softmax(beta * v), the exponent taken as (v - max) * beta -- beta = 1 multiplies by
 // 1.0f, which is exact, and gives the bytes of the plain form; without TEMP `beta` is not read and the code is the plain form's.
-template <int C, int N, bool TEMP = false>
-__device__ __forceinline__ void softmax_add(const ot_f32x4* __restrict__ src, float (&acc)[N], float beta = 1.f) {
+// WIN (pylc_blend_accumulate_w): acc[c] += wt * (v[c] * inv), the plain term times the tile's window weight before the
+// add -- wt = 1 is exact again; without WIN `wt` is not read.
+template <int C, int N, bool TEMP = false, bool WIN = false>
+__device__ __forceinline__ void softmax_add(const ot_f32x4* __restrict__ src, float (&acc)[N], float beta = 1.f, float wt = 1.f) {
     constexpr int NV = (C + 3) / 4;
     float v[NV * 4];
 #pragma unroll
@@ -58,7 +60,10 @@ __device__ __forceinline__ void softmax_add(const ot_f32x4* __restrict__ src, fl
     }
     const float inv = 1.f / s;
 #pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] += v[c] * inv;
+    for (int c = 0; c < C; ++c) {
+        if constexpr (WIN) acc[c] += wt * (v[c] * inv);
+        else acc[c] += v[c] * inv;
+    }
 }
 
 __device__ __forceinline__ int reflect101(int y, int n) {

@@ -15,6 +15,7 @@ that cover the image exactly, at any image size, blended by the mean of the tile
 import contextlib
 import ctypes as C
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -114,7 +115,7 @@ def _eval_mode(model):
 
 
 def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blend='reference', flip=False, return_probs=False,
-                  return_confidence=False, scales=None, scale_weights=None, temperature=None, refine=None):
+                  return_confidence=False, scales=None, scale_weights=None, temperature=None, refine=None, window=None):
     """image: [C,H,W] raw 0..255, uint8 or float (host or device), fitted.  Returns the uint8 class mask [H,W] (device).
 
     group=None (default): LOCAL -- this process runs every tile and returns the mask, also inside a data-parallel job (a rank-0-only
@@ -132,7 +133,9 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blen
     before every tile's softmax (pylc_blend_accumulate_t); like flip it needs blend='mean' and composes with flip and scales.
     refine ({'radius': 8, 'eps': 1e-3}, pylc_amd.refine.check_spec) passes the mean probabilities through the guided filter with the uint8
     image's luma as the guide (predict_blend_mean): the mask, probs and conf returned are the refined ones; like flip it
-    needs blend='mean'.
+    needs blend='mean'.  window ('hann', 'gauss', ('gauss', sigma_frac), 'uniform' or a table of `tile` positive floats; blend_window,
+    DESIGN.md 5.25) weighs every tile's probabilities by a separable window that falls off towards the tile's edge; like flip it needs
+    blend='mean', composes with the other keywords, and pays only where tiles overlap (stride < tile).
 
     A U-Net model (meta.arch == 'unet') takes predict_overlap_tile instead (any image size, stride default tile - 2*pad); its blend
     always was the mean, so `blend` is ignored and the other keywords pass through."""
@@ -140,13 +143,13 @@ def predict_image(model, image, tile=512, stride=None, batch=8, group=None, blen
         raise ValueError("blend is 'reference' or 'mean', got %r" % (blend,))
     if model.meta.arch == 'unet':
         return predict_overlap_tile(model, image, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights,
-                                    temperature, refine)
+                                    temperature, refine, window)
     if blend == 'mean':
         return predict_blend_mean(model, image, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights,
-                                  temperature, refine)
+                                  temperature, refine, window)
     asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence),
                             ('scales', scales is not None), ('scale_weights', scale_weights is not None),
-                            ('temperature', temperature is not None), ('refine', refine is not None)) if v]
+                            ('temperature', temperature is not None), ('refine', refine is not None), ('window', window is not None)) if v]
     if asked:
         raise ValueError("%s needs blend='mean': the reference stitch mixes logits and probabilities, its scores are not probabilities"
                          % ', '.join(asked))
@@ -217,7 +220,7 @@ def overlap_tile_out(net, tile, pad):
 
 
 def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=None, return_probs=False, flip=False, return_confidence=False,
-                         scales=None, scale_weights=None, temperature=None, refine=None):
+                         scales=None, scale_weights=None, temperature=None, refine=None, window=None):
     """Full-image U-Net inference by overlap tiles.  image: [C,H,W] raw 0..255, uint8 or float, host or device, any H, W >= out
     (out = tile - 2*meta.pad_size; no fitting).  stride in [1, out], default out.  Returns the uint8 class mask [H,W] (device), or
     (mask, probs) with probs the fp32 mean softmax probabilities [n_classes,H,W] when return_probs.
@@ -229,15 +232,19 @@ def predict_overlap_tile(model, image, tile=512, stride=None, batch=8, group=Non
 
     flip=True (the mirrored windows as a second ensemble member), return_confidence=True (the tuple grows by conf, fp32 [H,W], the
     maximum probability) or scales (the multi-scale ensemble) move the call to the streaming accumulator, predict_blend_mean; without
-    them it is the one-launch stitch.  So do temperature and refine (predict_image's keywords)."""
+    them it is the one-launch stitch.  So do temperature, refine and window (predict_image's keywords; the window table has `out`
+    entries and pays with stride < out)."""
     if model.meta.arch != 'unet':
         raise ValueError('predict_overlap_tile needs a U-Net (meta.arch == "unet"), got %r' % model.meta.arch)
+    if window is not None:
+        window_table(window, tile - 2 * model.meta.pad_size)          # argument errors before the device is touched
     L.init()
     pad = model.meta.pad_size
     out = overlap_tile_out(model.net, tile, pad)
-    if flip or return_confidence or scales is not None or scale_weights is not None or temperature is not None or refine is not None:
+    if (flip or return_confidence or scales is not None or scale_weights is not None or temperature is not None or refine is not None
+            or window is not None):
         return predict_blend_mean(model, image, tile, out, stride, batch, group, flip, return_probs, return_confidence, scales, scale_weights,
-                                  temperature, refine)
+                                  temperature, refine, window)
     stride = out if stride is None else int(stride)
     run = _TileRun(model, image, group)
     row_o, col_o = overlap_tile_grid(run.h, run.w, out, stride, pad)
@@ -323,10 +330,92 @@ def resolve_temperature(model, temperature):
     return 1.0 / t
 
 
-def _blend_sweep(run, img, tile, out, stride, batch, members, beta=None):
+WINDOW_MIN_RATIO = 2.0 ** -20       # min / max of a window table: below it a tile's edge has no say and fp32 sums lose the small terms
+_window_cache = {}
+
+
+def window_table(spec, out):
+    """The window `spec` as a host float32 numpy table [out], validated; needs no device.  Named windows are built in float64 and rounded
+    once: 'uniform' all ones; 'hann' 0.5 - 0.5*cos(2*pi*(i + 0.5)/out), the half-sample offset keeping every entry positive; 'gauss' or
+    ('gauss', sigma_frac) exp(-0.5*((i - (out - 1)/2)/(sigma_frac*out))**2), sigma_frac default 0.125 (nnU-Net's and MONAI's).  A 1-D
+    tensor or array of `out` floats is taken as given.  ValueError for an unknown name, a sigma_frac that is not positive and finite, a
+    wrong length, a non-finite or non-positive entry, or min / max < 2**-20."""
+    out = int(out)
+    if out < 1:
+        raise ValueError('window: output tile %d < 1' % out)
+    name, sigma = spec, None
+    if isinstance(spec, (tuple, list)) and len(spec) > 0 and isinstance(spec[0], str):
+        if len(spec) != 2 or spec[0] != 'gauss':
+            raise ValueError("window: a named window is 'uniform', 'hann', 'gauss' or ('gauss', sigma_frac), got %r" % (spec,))
+        name, sigma = spec
+    if isinstance(name, str):
+        i = np.arange(out, dtype=np.float64)
+        if name == 'uniform' and sigma is None:
+            tab = np.ones(out)
+        elif name == 'hann' and sigma is None:
+            tab = 0.5 - 0.5 * np.cos(2.0 * np.pi * (i + 0.5) / out)
+        elif name == 'gauss':
+            try:
+                sigma = 0.125 if sigma is None else float(sigma)
+            except (TypeError, ValueError):
+                raise ValueError('window: sigma_frac must be a positive finite number, got %r' % (spec[1],))
+            if not (sigma > 0.0 and sigma != float('inf')):
+                raise ValueError('window: sigma_frac must be a positive finite number, got %r' % (spec[1],))
+            tab = np.exp(-0.5 * ((i - (out - 1) / 2.0) / (sigma * out)) ** 2)
+        else:
+            raise ValueError("window: a named window is 'uniform', 'hann', 'gauss' or ('gauss', sigma_frac), got %r" % (spec,))
+        what = 'window %r at %d entries' % (spec, out)
+    else:
+        if torch.is_tensor(spec):
+            tab = spec.detach().cpu().numpy()
+        elif isinstance(spec, (np.ndarray, list, tuple)):
+            tab = np.asarray(spec)
+        else:
+            raise ValueError('window is None, a name, (\'gauss\', sigma_frac) or a 1-D table of floats, got %r' % (type(spec).__name__,))
+        if tab.ndim != 1 or tab.shape[0] != out or tab.dtype.kind not in 'fiu':
+            raise ValueError('window: a table has one float per pixel of the output tile, [%d]; got %s of %s' % (out, tuple(tab.shape), tab.dtype))
+        what = 'window table'
+    with np.errstate(over='ignore'):
+        tab = np.ascontiguousarray(tab.astype(np.float32))
+    if not np.isfinite(tab).all():
+        raise ValueError('%s has a non-finite entry' % what)
+    if not (tab > 0).all():
+        raise ValueError('%s has a non-positive entry (%g): a zero weight divides by zero where it is a pixel\'s only one' % (what, tab.min()))
+    if float(tab.min()) / float(tab.max()) < WINDOW_MIN_RATIO:
+        raise ValueError('%s: min / max = %g is below 2**-20' % (what, float(tab.min()) / float(tab.max())))
+    return tab
+
+
+def blend_window(spec, out, device):
+    """The window of the window-weighted blend as the float32 device table [out] that pylc_blend_accumulate_w and
+    pylc_blend_window_sums read.  spec: window_table's -- 'uniform', 'hann', 'gauss', ('gauss', sigma_frac), or a 1-D tensor / array of
+    `out` positive floats; its ValueErrors are raised before the device is touched.  Named windows are cached per (spec, out, device)."""
+    named = isinstance(spec, str) or (isinstance(spec, (tuple, list)) and len(spec) > 0 and isinstance(spec[0], str))
+    key = None
+    if named:
+        try:
+            key = (spec if isinstance(spec, str) else (spec[0],) + tuple(float(v) for v in spec[1:]), int(out), str(torch.device(device)))
+        except (TypeError, ValueError):
+            key = None                                                  # window_table raises on it
+        if key in _window_cache:
+            return _window_cache[key]
+    tab = torch.from_numpy(window_table(spec, out)).to(device)
+    if key is not None:
+        _window_cache[key] = tab
+    return tab
+
+
+def _window_sums(win, out, stride, n):
+    """pylc_blend_window_sums: the table [n] of an axis of length n"""
+    sums = torch.empty((n,), device=win.device)
+    check(lib.pylc_blend_window_sums(ptr(win), out, stride, n, ptr(sums), stream()))
+    return sums
+
+
+def _blend_sweep(run, img, tile, out, stride, batch, members, beta=None, win=None):
     """predict_blend_mean's sweep over one device image [C,H,W] (uint8 or float32; run.img or another size of it): this rank's share of
     the tile batches, member-major, into a zeroed accumulation image [H,W,cp], which it returns.  The network is in eval mode already.
-    beta: None, or the inverse temperature of pylc_blend_accumulate_t."""
+    beta: None, or the inverse temperature of pylc_blend_accumulate_t.  win: None, or blend_window's table: pylc_blend_accumulate_w."""
     h, w = img.shape[1:]
     row_o, col_o = overlap_tile_grid(h, w, out, stride, (tile - out) // 2)
     mine = run.mine(len(row_o) * len(col_o), batch)
@@ -342,7 +431,10 @@ def _blend_sweep(run, img, tile, out, stride, batch, members, beta=None):
                 y2 = ops.zeros_nhwc(b, ncls, out, out, run.dev, pitch=cp)
                 y2.copy_(y)
                 y, p = y2, cp
-            if beta is None:
+            if win is not None:
+                check(lib.pylc_blend_accumulate_w(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, ptr(win),
+                                                  1.0 if beta is None else beta, stream()))
+            elif beta is None:
                 check(lib.pylc_blend_accumulate(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream()))
             else:
                 check(lib.pylc_blend_accumulate_t(ptr(y), p, k, b, h, w, out, stride, ncls, member, ptr(acc), cp, stream(), beta))
@@ -350,7 +442,7 @@ def _blend_sweep(run, img, tile, out, stride, batch, members, beta=None):
 
 
 def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None, flip=False, return_probs=False, return_confidence=False,
-                       scales=None, scale_weights=None, temperature=None, refine=None):
+                       scales=None, scale_weights=None, temperature=None, refine=None, window=None):
     """The streaming mean-probability blend (csrc/blend.hip) for a network that maps a `tile` window to its centred `out`
     square (DeepLab: out = tile; U-Net: out = tile - 2*pad).  image: [C,H,W] raw 0..255, uint8 or float, any H, W >= out; stride in
     [1, out], default tile // 2 for a same-size network and out otherwise.
@@ -383,8 +475,16 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
     scales and temperature.  The image must be uint8 (ValueError otherwise).  Memory: the filter's coefficients are two more volumes the
     size of probs, 2 * 4 * C * H * W bytes -- 0.9 GB on a 3072 x 4096 photograph with 9 classes -- allocated after the accumulation
     images above are done with.  None enters nothing new.
+    window: None, or blend_window's spec.  With one, a tile's probabilities count win[ly] * win[lx] times at the pixel at
+    (ly, lx) of the placed tile -- the same table for every member and scale -- through pylc_blend_accumulate_w, and the finalizer (with
+    scales: every size's resample step) divides by members * sum_y[y] * sum_x[x], two per-axis tables of pylc_blend_window_sums,
+    (H + W) * 4 bytes more.  'uniform' gives the bytes of None.  A pixel that one tile covers gets that tile's probabilities back to a
+    rounding, so the knob pays only with stride < out; it is not refused otherwise.  flip, temperature, group and refine compose as
+    above (the accumulate step stays linear in the per-rank images).  None enters nothing new.
     Returns mask, or (mask[, probs][, conf])."""
     beta = resolve_temperature(model, temperature)                     # before any launch
+    if window is not None:
+        window_table(window, out)                                      # its errors too
     spec = None
     if refine is not None:
         from . import refine as _refine
@@ -403,16 +503,23 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
     img, h, w, ncls, cp = run.img, run.h, run.w, run.ncls, run.cp
     overlap_tile_grid(h, w, out, stride, (tile - out) // 2)            # the geometry's errors before the network's mode is touched
     members = 2 if flip else 1
+    win = None if window is None else blend_window(window, out, run.dev)
     acc = ens = None
     with _eval_mode(model):
         if plan is None:
-            acc = _blend_sweep(run, img, tile, out, stride, batch, members, beta)
+            acc = _blend_sweep(run, img, tile, out, stride, batch, members, beta, win)
         else:
             ens = torch.empty((h, w, cp), device=run.dev)             # the first scale's launch writes every channel below ncls
             for k, (_, hs, ws, wgt) in enumerate(plan):
-                acc_s = _blend_sweep(run, img if (hs, ws) == (h, w) else resize_image(img, hs, ws), tile, out, stride, batch, members, beta)
-                check(lib.pylc_blend_resample_accumulate(ptr(acc_s), cp, hs, ws, out, stride, members, wgt, ncls, ptr(ens), cp, h, w,
-                                                         int(k > 0), stream()))
+                acc_s = _blend_sweep(run, img if (hs, ws) == (h, w) else resize_image(img, hs, ws), tile, out, stride, batch, members, beta, win)
+                if win is None:
+                    check(lib.pylc_blend_resample_accumulate(ptr(acc_s), cp, hs, ws, out, stride, members, wgt, ncls, ptr(ens), cp, h, w,
+                                                             int(k > 0), stream()))
+                else:
+                    sy, sx = _window_sums(win, out, stride, hs), _window_sums(win, out, stride, ws)
+                    check(lib.pylc_blend_resample_accumulate_w(ptr(acc_s), cp, hs, ws, members, wgt, ncls, ptr(sy), ptr(sx), ptr(ens), cp, h, w,
+                                                               int(k > 0), stream()))
+                    del sy, sx
                 del acc_s
     if run.world > 1:
         if plan is not None:
@@ -422,18 +529,22 @@ def predict_blend_mean(model, image, tile, out, stride=None, batch=8, group=None
             return None
     total = None if plan is None else sum(p[3] for p in plan)
     if spec is None:
-        return _blend_finalize(acc if plan is None else ens, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, total)
-    _, probs = _blend_finalize(acc if plan is None else ens, cp, h, w, out, stride, ncls, members, True, False, total)
+        return _blend_finalize(acc if plan is None else ens, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, total, win)
+    _, probs = _blend_finalize(acc if plan is None else ens, cp, h, w, out, stride, ncls, members, True, False, total, win)
     del acc, ens
     return _refine.guided_refine(probs, img, spec[0], spec[1], return_probs, return_confidence, spec[2])
 
 
-def _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, total_weight=None):
-    """mask[, probs][, conf] from a blend's sums (divided by the geometry's counts) or, with total_weight, from an ensemble image"""
+def _blend_finalize(acc, cp, h, w, out, stride, ncls, members, return_probs, return_confidence, total_weight=None, win=None):
+    """mask[, probs][, conf] from a blend's sums (divided by the geometry's counts or, with the window table `win`, by the two axis
+    tables of its sums) or, with total_weight, from an ensemble image (the resample step has divided already)"""
     mask = torch.empty((h, w), device=acc.device, dtype=torch.uint8)
     probs = torch.empty((ncls, h, w), device=acc.device) if return_probs else None
     conf = torch.empty((h, w), device=acc.device) if return_confidence else None
-    if total_weight is None:
+    if total_weight is None and win is not None:
+        sy, sx = _window_sums(win, out, stride, h), _window_sums(win, out, stride, w)
+        check(lib.pylc_blend_finalize_w(ptr(acc), cp, h, w, ncls, members, ptr(sy), ptr(sx), ptr(mask), ptr(probs), ptr(conf), stream()))
+    elif total_weight is None:
         check(lib.pylc_blend_finalize(ptr(acc), cp, h, w, out, stride, ncls, members, ptr(mask), ptr(probs), ptr(conf), stream()))
     else:
         check(lib.pylc_ensemble_finalize(ptr(acc), cp, h, w, ncls, total_weight, ptr(mask), ptr(probs), ptr(conf), stream()))

@@ -207,6 +207,10 @@ SIGNATURES = {
     'pylc_resize_bilinear_image': (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
     'pylc_blend_resample_accumulate': (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _I, _I, _I, _I, _P]),
     'pylc_ensemble_finalize': (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    'pylc_blend_accumulate_w': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _F, _P]),
+    'pylc_blend_window_sums': (_I, [_P, _I, _I, _I, _P, _P]),
+    'pylc_blend_finalize_w': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'pylc_blend_resample_accumulate_w': (_I, [_P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'pylc_image_pack_denom': (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _F, _P, _P]),
     'pylc_image_pack_u8': (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     'pylc_extract_tiles': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

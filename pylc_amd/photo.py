@@ -188,7 +188,7 @@ def _sieve_result(res, pal, min_region, connectivity, fill, ignore_index):
 
 def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None, batch=8, group=None, return_probs=False, blend='reference',
                   flip=False, return_confidence=False, min_region=0, region_connectivity=4, region_fill='neighbour', ignore_index=None,
-                  scales=None, scale_weights=None, temperature=None, refine=None):
+                  scales=None, scale_weights=None, temperature=None, refine=None, window=None):
     """A decoded photograph ([H,W,3] RGB or [H,W] / [H,W,1] grayscale uint8, numpy or tensor) -> PhotoResult at the scaled size.
 
     DeepLab, blend='reference' (default): fit (stride default tile // 2, test.py:63), predict_image's sliding window on the uint8 fitted
@@ -204,7 +204,9 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     model.meta.temperature) divides the logits before every tile's softmax, under the same condition.
     refine ({'radius': 8, 'eps': 1e-3}) passes the mean probabilities through the guided filter with the scaled-size
     photograph's luma as the guide, under the same condition: mask, probs and confidence are the refined ones, and the order is refine ->
-    colourize / encode -> sieve.
+    colourize / encode -> sieve.  window ('hann', 'gauss', ('gauss', sigma_frac), 'uniform' or a table of one float per pixel of the output
+    tile; inference.blend_window) weighs every tile's probabilities by a window that falls off towards the tile's edge,
+    under the same condition; it pays only with stride below the output tile, and refine and the sieve act on its result.
 
     min_region > 1: regions of the final mask below that many pixels are sieved (regions.sieve with region_connectivity, region_fill and
     ignore_index; one pass), PhotoResult.rgb is recoloured from the sieved mask and PhotoResult.n_sieved counts the replaced pixels.  A
@@ -224,7 +226,8 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     if not unet and blend == 'reference':
         asked = [k for k, v in (('flip', flip), ('return_probs', return_probs), ('return_confidence', return_confidence),
                                 ('scales', scales is not None), ('scale_weights', scale_weights is not None),
-                                ('temperature', temperature is not None), ('refine', refine is not None)) if v]
+                                ('temperature', temperature is not None), ('refine', refine is not None),
+                                ('window', window is not None)) if v]
         if asked:
             raise ValueError("%s needs blend='mean' on a DeepLab: the reference sliding-window stitch mixes logits and probabilities, its "
                              "scores are not probabilities" % ', '.join(asked))
@@ -233,6 +236,9 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
     if refine is not None:
         from .refine import check_spec
         check_spec(refine)
+    if window is not None:
+        from .inference import window_table
+        window_table(window, tile - 2 * model.meta.pad_size if unet else tile)
     sieving = int(min_region) > 1
     if sieving:
         regions._check_mask(torch.empty((1, 1), dtype=torch.uint8), region_connectivity, ignore_index)
@@ -250,10 +256,10 @@ def segment_photo(model, image, tile=512, stride=None, scale=None, palette=None,
         img = resize_area(_upload_photo(image, dev), h_s, w_s)      # at its own size: a relayout to [C,H,W]
         if unet:
             got = predict_overlap_tile(model, img, tile, stride, batch, group, return_probs, flip, return_confidence, scales, scale_weights,
-                                       temperature, refine)
+                                       temperature, refine, window)
         else:
             got = predict_blend_mean(model, img, tile, tile, stride, batch, group, flip, return_probs, return_confidence, scales,
-                                     scale_weights, temperature, refine)
+                                     scale_weights, temperature, refine, window)
         if got is None:
             return None
         got = list(got) if isinstance(got, tuple) else [got]

@@ -13,7 +13,13 @@ warm-up, the forms taking turns within a round (--rounds, the median is reported
 its batch covers (counted on the host from the geometry), the finalizer reads the accumulation image once.  `resident` is what each
 form needs in HBM at its peak besides the image: all tiles, or one batch of tiles plus the accumulation image.
 
-    python tools/blend_bench.py [--batch B] [--rounds R] [--warmup W] [--out FILE]
+--window adds the window-weighted legs after the rows above, which are measured and printed as before: in a
+second loop of the same warm-up and round counts the plain streaming form (zero, pylc_blend_accumulate, pylc_blend_finalize) and the
+windowed one (zero, pylc_blend_accumulate_w with the Hann table of 512 floats, pylc_blend_finalize_w with the two axis tables, built
+once outside the timing) take turns.  Its JSON line holds, per phase, the median and the min / max over the rounds of both forms, and
+`slower_than_spread`: whether the windowed median exceeds the plain median by more than the plain form's own min-max spread.
+
+    python tools/blend_bench.py [--batch B] [--rounds R] [--warmup W] [--out FILE] [--window [--window-out FILE]]
 """
 import argparse
 import json
@@ -35,6 +41,8 @@ def main():
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--window', action='store_true')
+    ap.add_argument('--window-out', default=None)
     a = ap.parse_args()
     from pylc_amd import lib as L
     from pylc_amd.inference import overlap_tile_grid, tile_grid
@@ -125,6 +133,58 @@ def main():
     if a.out:
         with open(a.out, 'w') as f:
             f.write(line + '\n')
+    if not a.window:
+        return
+
+    # ---- the window-weighted legs: the plain and the windowed streaming form take turns ------------------------------------------------
+    from pylc_amd.inference import blend_window, _window_sums
+    win = blend_window('hann', TILE, dev)
+    sum_y, sum_x = _window_sums(win, TILE, STRIDE, H), _window_sums(win, TILE, STRIDE, W)
+
+    def accumulate_w():
+        for k, b in batches:
+            check(lib.pylc_blend_accumulate_w(ptr(logits[k:k + b]), PITCH, k, b, H, W, TILE, STRIDE, C, 0, ptr(acc), PITCH, ptr(win), 1.0, st))
+
+    def finalize_w():
+        check(lib.pylc_blend_finalize_w(ptr(acc), PITCH, H, W, C, 1, ptr(sum_y), ptr(sum_x), ptr(masks['streaming']), None, None, st))
+
+    # a table of ones gives the plain form's bytes, first
+    ones = blend_window('uniform', TILE, dev)
+    acc.zero_()
+    accumulate()
+    want = acc.clone()
+    acc.zero_()
+    for k, b in batches:
+        check(lib.pylc_blend_accumulate_w(ptr(logits[k:k + b]), PITCH, k, b, H, W, TILE, STRIDE, C, 0, ptr(acc), PITCH, ptr(ones), 1.0, st))
+    torch.cuda.synchronize()
+    if not torch.equal(acc, want):
+        raise SystemExit('pylc_blend_accumulate_w with a table of ones differs from pylc_blend_accumulate')
+    del want
+
+    wforms = {'plain': [acc.zero_, accumulate, finalize], 'windowed': [acc.zero_, accumulate_w, finalize_w]}
+    wtimes = {k: [] for k in wforms}
+    for r in range(a.warmup + a.rounds):
+        for k, fns in wforms.items():
+            t = span(fns)
+            if r >= a.warmup:
+                wtimes[k].append(t)
+    phases = {}
+    for j, name in ((1, 'accumulate'), (2, 'finalize')):
+        col = {k: np.asarray(v)[:, j] * 1e6 for k, v in wtimes.items()}
+        spread = float(col['plain'].max() - col['plain'].min())
+        phases[name] = {'plain_us': float(np.median(col['plain'])), 'plain_min_max_us': [float(col['plain'].min()), float(col['plain'].max())],
+                        'windowed_us': float(np.median(col['windowed'])),
+                        'windowed_min_max_us': [float(col['windowed'].min()), float(col['windowed'].max())],
+                        'plain_spread_us': spread,
+                        'slower_than_spread': bool(np.median(col['windowed']) - np.median(col['plain']) > spread)}
+    wout = {'image': [H, W], 'n_classes': C, 'pitch': PITCH, 'tile': TILE, 'stride': STRIDE, 'tiles': n, 'batch': a.batch, 'window': 'hann',
+            'rounds': a.rounds, 'warmup': a.warmup, 'device': torch.cuda.get_device_name(0), 'host': platform.node(),
+            'table_bytes': {'window': TILE * 4, 'axis_sums': (H + W) * 4}, 'phases': phases}
+    wline = json.dumps(wout)
+    print(wline)
+    if a.window_out:
+        with open(a.window_out, 'w') as f:
+            f.write(wline + '\n')
 
 
 if __name__ == '__main__':
