@@ -806,6 +806,29 @@ int pylc_augment_tiles(const unsigned char* img_tiles, const unsigned char* mask
                        const int* src_index, const double* minv, const int* shift, long long m, int band_rows,
                        unsigned char* out_img, unsigned char* out_mask, int n_classes, unsigned long long* sums,
                        unsigned long long* hist, void* stream);
+/* The per-step training augmenter (csrc/batch_augment.hip; the definition: DESIGN.md section 5.26): output sample k (k < m) is source
+ * plane set src_index[k] of img [n_src][Cimg][Hs][Ws] (and of mask [n_src][Hs][Ws] and weights fp32 [n_src][Hs][Ws] when given) under
+ * the INVERSE affine map mats[k] = (a00, a01, a02, a10, a11, a12), int64 in Q24 fixed point.  For output pixel (x, y), centres at integers:
+ *   X = a00 x + a01 y + a02, Y = a10 x + a11 y + a12 (int64);
+ *   image: sx = X >> 24, fx = (X >> 19) & 31, likewise sy, fy (floor);
+ *          N = (t(sy,sx)(32-fx) + t(sy,sx+1) fx)(32-fy) + (t(sy+1,sx)(32-fx) + t(sy+1,sx+1) fx) fy; out = lut[k][c][(N + 512) >> 10]
+ *          (lut: device uint8 [m][Cimg][256]; NULL is the identity);
+ *   mask and weights (nearest): mx = (X + 2^23) >> 24, my likewise.
+ * border PYLC_BORDER_CONSTANT: a tap outside the source reads fill[c] (HOST uint8 [Cimg]), a mask pixel outside is mask_fill (0..255),
+ * a weight outside 0.0f.  PYLC_BORDER_REFLECT: BORDER_REFLECT_101 on the indices (period 2(n-1)) for any integer; fill may be NULL.
+ * All integer arithmetic: exact, and independent of band_rows (output rows per block, 0 for the default).  The entry point draws nothing.
+ * out_img [m][Cimg][oh][ow], out_mask [m][oh][ow], out_weights fp32 [m][oh][ow] (4-B aligned); an output exactly where its source is
+ * given.  src_index and mats may each be a device buffer or a HOST array: host arrays are checked here and travel as kernel arguments
+ * (32 samples per launch; device buffers: one launch).  Cimg 1 or 3, Hs, Ws >= 2, Hs * Ws < 2^31, 1 <= oh, ow <= 16384,
+ * |a00|, |a01|, |a10|, |a11| <= 2^32 (a magnification of 1/256 at the least) and |a02|, |a12| < 2^44 (int64 then cannot overflow);
+ * otherwise, or with a host src_index entry outside 0 .. n_src - 1: PYLC_ERR_ARG, nothing is launched.  A sample whose DEVICE index or
+ * matrix breaks these bounds is the caller's error and is left unwritten. */
+#define PYLC_BORDER_CONSTANT 0
+#define PYLC_BORDER_REFLECT 1
+int pylc_batch_augment(const unsigned char* img, const unsigned char* mask, const float* weights, long long n_src, int Cimg, int Hs,
+                       int Ws, const int* src_index, const long long* mats, const unsigned char* lut, long long m, int oh, int ow,
+                       int border, const unsigned char* fill, int mask_fill, int band_rows, unsigned char* out_img,
+                       unsigned char* out_mask, float* out_weights, void* stream);
 
 /* Confusion matrix cm[t*C + p] += 1 over n pixels of class-index masks (uint8 or int64; *_bytes = 1 or 8); the scores of
  * utils/metrics.py:64-88 (weighted F1, weighted IoU = the "mIoU", MCC, normalised matrix) are functions of it.

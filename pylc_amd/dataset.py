@@ -18,6 +18,10 @@ The augmented copies those rates ask for (Augmentor.oversample -> augment_transf
 are made by pylc_augment_tiles: augment_params draws a copy's warp and brightness shift as the reference does, augment_tiles applies them
 on the device, TileSet.oversample composes the class-balanced set.
 
+Not in the reference: the per-step augmenter -- random scale, rotation, mirror image, crop and a tone curve drawn
+anew for every batch: batch_augment_params draws, augment_batch applies them by one launch of pylc_batch_augment (exact integer
+arithmetic), TileSet.batches(augment=...) feeds Model.train with them.
+
 Out of scope: HDF5 files, file collation, print_meta."""
 import math
 
@@ -190,6 +194,179 @@ def oversample_layout(rates):
     first = np.cumsum(rates + 1) - (rates + 1)
     copy = np.arange(src.size, dtype=np.int64) - first[src] - 1
     return src, copy
+
+
+# ---- the per-step augmenter --------------------------------------------------------------------------------------------------------
+Q24 = 1 << 24
+BORDERS = {'constant': 0, 'reflect': 1}                    # PYLC_BORDER_* (include/pylc_hip.h)
+MAT_LINEAR_MAX = 1 << 32                                   # |a00|, |a01|, |a10|, |a11| <= 2^32: a magnification of 1/256 at the least
+MAT_SHIFT_LIMIT = 1 << 44                                  # |a02|, |a12| < 2^44: int64 cannot overflow for outputs up to 16384
+AUG_MAX_OUT = 16384
+
+
+def tone_lut(brightness=0.0, contrast=1.0, gamma=1.0, ch=3):
+    """The photometric step of the per-step augmenter as a table, uint8 [ch, 256]: in float64, for v = 0..255,
+    rint(255 * (clip(contrast * (v - 128) + 128 + brightness, 0, 255) / 255) ** gamma).  Each argument is a scalar or one value per
+    channel.  The kernel does one lookup per byte, so any other per-channel curve fits the same table."""
+    v = np.arange(256, dtype=np.float64)[None, :]
+
+    def per_channel(a, what):
+        a = np.asarray(a, dtype=np.float64).reshape(-1)
+        if a.size not in (1, ch):
+            raise ValueError('%s: %d values for %d channels' % (what, a.size, ch))
+        return np.broadcast_to(a, (ch,))[:, None]
+    b, c, g = per_channel(brightness, 'brightness'), per_channel(contrast, 'contrast'), per_channel(gamma, 'gamma')
+    if (g <= 0).any():
+        raise ValueError('gamma must be positive')
+    return np.rint(255.0 * (np.clip(c * (v - 128.0) + 128.0 + b, 0.0, 255.0) / 255.0) ** g).astype(np.uint8)
+
+
+def affine_q24(src_hw, out_hw, scale=1.0, rotate_deg=0.0, flip_x=False, flip_y=False, centre_xy=None):
+    """The inverse affine map of one sample, int64 [6] = (a00, a01, a02, a10, a11, a12) in Q24: output pixel (x, y) reads the source at
+    L (x, y) + b with L = (1 / scale) [[cos, sin], [-sin, cos]] diag(-1 if flip_x else 1, -1 if flip_y else 1) and
+    b = centre - L ((ow - 1) / 2, (oh - 1) / 2): the output's centre looks at centre_xy of the source (default: its centre,
+    ((Ws - 1) / 2, (Hs - 1) / 2)), magnified by `scale` and turned by rotate_deg.  Every entry is rint(value * 2^24)."""
+    (hs, ws), (oh, ow) = src_hw, out_hw
+    if not scale > 0:
+        raise ValueError('scale=%s must be positive' % (scale,))
+    cx, cy = ((ws - 1) / 2.0, (hs - 1) / 2.0) if centre_xy is None else centre_xy
+    t = math.radians(rotate_deg)
+    lin = np.array([[math.cos(t), math.sin(t)], [-math.sin(t), math.cos(t)]]) / float(scale)
+    lin = lin * np.array([-1.0 if flip_x else 1.0, -1.0 if flip_y else 1.0])[None, :]
+    b = np.array([cx, cy], dtype=np.float64) - lin @ np.array([(ow - 1) / 2.0, (oh - 1) / 2.0])
+    return np.rint(np.array([lin[0, 0], lin[0, 1], b[0], lin[1, 0], lin[1, 1], b[1]]) * Q24).astype(np.int64)
+
+
+def _range(v, what):
+    lo, hi = (v, v) if np.isscalar(v) else v
+    if not lo <= hi:
+        raise ValueError('%s range (%s, %s)' % (what, lo, hi))
+    return float(lo), float(hi)
+
+
+def batch_augment_params(rs, m, src_hw, out_hw, scale=(0.5, 2.0), rotate=0.0, flip=0.5, vflip=0.0, brightness=(0, 0), contrast=(1, 1),
+                         gamma=(1, 1), ch=3):
+    """The draws of m samples from the numpy RandomState rs -> (mats int64 [m,6], luts uint8 [m,ch,256], or None when the three tone
+    ranges are all trivial -- (0, 0), (1, 1), (1, 1)).  Per sample, NINE draws in this order, every one of them made whatever the ranges:
+        1. scale       rs.uniform(scale_lo, scale_hi)
+        2. angle       rs.uniform(-rotate, rotate), degrees
+        3. flip_x      rs.uniform() < flip
+        4. flip_y      rs.uniform() < vflip
+        5. ux          rs.uniform(-1, 1)
+        6. uy          rs.uniform(-1, 1)
+        7. brightness  rs.uniform(lo, hi)         8. contrast  rs.uniform(lo, hi)         9. gamma  rs.uniform(lo, hi)
+    The window's centre is ((Ws - 1) / 2 + ux (Ws - ow / scale) / 2, (Hs - 1) / 2 + uy (Hs - oh / scale) / 2): the crop moves inside
+    the source where it fits, and the source inside the crop where it does not.  The matrix is affine_q24 of these; the table is
+    tone_lut of the three tone values, shared by the channels.  A range may be given as one number (no spread)."""
+    (hs, ws), (oh, ow) = src_hw, out_hw
+    s_lo, s_hi = _range(scale, 'scale')
+    if not s_lo > 0:
+        raise ValueError('scale range (%s, %s) must be positive' % (s_lo, s_hi))
+    if rotate < 0 or not 0 <= flip <= 1 or not 0 <= vflip <= 1:
+        raise ValueError('rotate=%s flip=%s vflip=%s' % (rotate, flip, vflip))
+    tone = [_range(brightness, 'brightness'), _range(contrast, 'contrast'), _range(gamma, 'gamma')]
+    with_lut = tone != [(0.0, 0.0), (1.0, 1.0), (1.0, 1.0)]
+    mats = np.empty((m, 6), np.int64)
+    luts = np.empty((m, ch, 256), np.uint8) if with_lut else None
+    for k in range(m):
+        sc = rs.uniform(s_lo, s_hi)
+        angle = rs.uniform(-rotate, rotate)
+        fx = rs.uniform() < flip
+        fy = rs.uniform() < vflip
+        ux, uy = rs.uniform(-1, 1), rs.uniform(-1, 1)
+        b, c, g = (rs.uniform(lo, hi) for lo, hi in tone)
+        centre = ((ws - 1) / 2.0 + ux * (ws - ow / sc) / 2.0, (hs - 1) / 2.0 + uy * (hs - oh / sc) / 2.0)
+        mats[k] = affine_q24(src_hw, out_hw, sc, angle, fx, fy, centre)
+        if with_lut:
+            luts[k] = tone_lut(b, c, g, ch)
+    return mats, luts
+
+
+def check_affine_q24(mats):
+    """ValueError for matrices pylc_batch_augment refuses: |a00|, |a01|, |a10|, |a11| > 2^32 or |a02|, |a12| >= 2^44."""
+    mats = np.asarray(mats)
+    if mats.dtype != np.int64 or mats.ndim != 2 or mats.shape[1] != 6:
+        raise ValueError('matrices must be int64 [m,6] in Q24, got %s %s' % (mats.dtype, mats.shape))
+    lin, shift = mats[:, [0, 1, 3, 4]], mats[:, [2, 5]]
+    if mats.size and ((lin > MAT_LINEAR_MAX) | (lin < -MAT_LINEAR_MAX)).any():
+        raise ValueError('a matrix entry a00, a01, a10 or a11 beyond 2^32 in Q24: a magnification below 1/256')
+    if mats.size and ((shift >= MAT_SHIFT_LIMIT) | (shift <= -MAT_SHIFT_LIMIT)).any():
+        raise ValueError('a matrix entry a02 or a12 at or beyond 2^44 in Q24: a translation of 2^20 pixels')
+    return np.ascontiguousarray(mats)
+
+
+def augment_batch(img, mask, src_index, mats, luts=None, out_hw=None, border='constant', fill=None, mask_fill=None, weights=None,
+                  band_rows=0):
+    """pylc_batch_augment: sample k is source src_index[k] of the device uint8 planes img [n,C,Hs,Ws] (C 1 or 3; tiles, or one whole
+    photograph with n = 1), of the uint8 masks [n,Hs,Ws] and of the float32 weight maps [n,Hs,Ws] (either may be None), under the inverse
+    affine map mats[k] (int64 [m,6] in Q24: affine_q24, batch_augment_params) and the tone tables luts[k] (uint8 [m,C,256] or None),
+    at out_hw (default: the source's size).  The image is sampled bilinearly, mask and weights by the nearest pixel -- the SAME pixel.
+    border='constant': outside the source the image is fill (one value per channel, default 0), the mask mask_fill (required with a
+    mask: the ignore label) and the weight 0; border='reflect': BORDER_REFLECT_101.  src_index and mats are host arrays (they travel as
+    kernel arguments, 32 samples per launch) or device tensors (int32 / int64: one launch; they are read back here to be checked).
+    Returns (img uint8 [m,C,oh,ow], mask uint8 [m,oh,ow] or None, weights float32 [m,oh,ow] or None) on the device.  Everything the
+    entry point refuses is refused here, with a ValueError, before anything is launched.  band_rows changes the launch only."""
+    if img.dtype != torch.uint8 or img.dim() != 4:
+        raise ValueError('sources must be uint8 [n,C,Hs,Ws], got %s %s' % (img.dtype, tuple(img.shape)))
+    n, c, hs, ws = img.shape
+    if c not in (1, 3):
+        raise ValueError('C=%d, not 1 or 3' % c)
+    if n < 1 or hs < 2 or ws < 2 or hs * ws >= 1 << 31:
+        raise ValueError('%d sources of %dx%d (HxW): at least one, of 2x2 or more' % (n, hs, ws))
+    oh, ow = (hs, ws) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if not (1 <= oh <= AUG_MAX_OUT and 1 <= ow <= AUG_MAX_OUT):
+        raise ValueError('output %dx%d (HxW) outside 1..%d' % (oh, ow, AUG_MAX_OUT))
+    if border not in BORDERS:
+        raise ValueError("border must be 'constant' or 'reflect', got %r" % (border,))
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (n, hs, ws)):
+        raise ValueError('masks must be uint8 %s, got %s %s' % ((n, hs, ws), mask.dtype, tuple(mask.shape)))
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (n, hs, ws)):
+        raise ValueError('weights must be float32 %s, got %s %s' % ((n, hs, ws), weights.dtype, tuple(weights.shape)))
+    if border == 'constant' and mask is not None and mask_fill is None:
+        raise ValueError("border='constant' with a mask needs mask_fill (the ignore label)")
+    mask_fill = 0 if mask_fill is None else int(mask_fill)
+    if not 0 <= mask_fill <= 255:
+        raise ValueError('mask_fill=%d outside 0..255' % mask_fill)
+    fill = np.zeros(c, np.int64) if fill is None else np.asarray(fill).reshape(-1)
+    if fill.size == 1:
+        fill = np.repeat(fill, c)
+    if fill.size != c or (fill < 0).any() or (fill > 255).any() or (fill != np.rint(fill)).any():
+        raise ValueError('fill must be one uint8 value per channel, got %s' % (fill,))
+    fill = np.ascontiguousarray(fill.astype(np.uint8))
+    d_src = src_index if torch.is_tensor(src_index) and src_index.is_cuda else None
+    if d_src is not None and (d_src.dtype != torch.int32 or not d_src.is_contiguous()):
+        raise ValueError('a device src_index must be a contiguous int32 tensor')
+    src = np.asarray(src_index.cpu() if torch.is_tensor(src_index) else src_index).reshape(-1)
+    if src.size and not np.issubdtype(src.dtype, np.integer):
+        raise ValueError('src_index must hold integers')
+    m = src.shape[0]
+    if m and (src.min() < 0 or src.max() >= n):
+        raise ValueError('src_index outside 0..%d' % (n - 1))
+    src = np.ascontiguousarray(src.astype(np.int32))
+    d_mats = mats if torch.is_tensor(mats) and mats.is_cuda else None
+    if d_mats is not None and not d_mats.is_contiguous():
+        raise ValueError('device matrices must be contiguous')
+    mats = check_affine_q24(mats.cpu().numpy() if torch.is_tensor(mats) else mats)
+    if mats.shape[0] != m:
+        raise ValueError('%d source indices, %d matrices' % (m, mats.shape[0]))
+    if luts is not None:
+        if not torch.is_tensor(luts):
+            luts = torch.from_numpy(np.ascontiguousarray(luts))
+        if luts.dtype != torch.uint8 or tuple(luts.shape) != (m, c, 256):
+            raise ValueError('tone tables must be uint8 %s, got %s %s' % ((m, c, 256), luts.dtype, tuple(luts.shape)))
+    L.init()
+    dev = img.device
+    img = img.contiguous()
+    mask = mask.contiguous() if mask is not None else None
+    weights = weights.contiguous() if weights is not None else None
+    luts = luts.to(dev).contiguous() if luts is not None else None
+    out = torch.empty((m, c, oh, ow), device=dev, dtype=torch.uint8)
+    mout = torch.empty((m, oh, ow), device=dev, dtype=torch.uint8) if mask is not None else None
+    wout = torch.empty((m, oh, ow), device=dev, dtype=torch.float32) if weights is not None else None
+    check(lib.pylc_batch_augment(ptr(img), ptr(mask), ptr(weights), n, c, hs, ws, ptr(d_src) if d_src is not None else src.ctypes.data,
+                                 ptr(d_mats) if d_mats is not None else mats.ctypes.data, ptr(luts), m, oh, ow, BORDERS[border],
+                                 fill.ctypes.data, mask_fill, band_rows, ptr(out), ptr(mout), ptr(wout), stream()))
+    return out, mout, wout
 
 
 class Extracted:
@@ -426,6 +603,42 @@ class _Batches:
                 yield img[lo:hi].numpy(), (mask[lo:hi].numpy() if mask is not None else None)
 
 
+class _AugmentedBatches:
+    """re-iterable over a TileSet's batches, each augmented anew (batch_augment_params -> augment_batch): device (img uint8 [B,C,oh,ow],
+    mask uint8 [B,oh,ow] or None).  ONE RandomState(seed) belongs to the iterable and advances across iterations: every epoch differs, and
+    a run with the same seed repeats."""
+
+    def __init__(self, tiles, batch_size, drop_last, augment, seed, out, device):
+        self.plain = _Batches(tiles, batch_size, drop_last)
+        self.tiles, self.augment, self.device = tiles, dict(augment), device
+        self.out_hw = (tiles.tile, tiles.tile) if out is None else ((int(out), int(out)) if np.isscalar(out) else (int(out[0]), int(out[1])))
+        batch_augment_params(np.random.RandomState(0), 0, (tiles.tile, tiles.tile), self.out_hw, ch=tiles.ch, **self.augment)      # the keywords
+        self.rs = np.random.RandomState(seed)
+
+    def __len__(self):
+        return len(self.plain)
+
+    def __iter__(self):
+        ts, bs = self.tiles, self.plain.batch_size
+        img, mask = ts._storage()
+        kw = {'border': 'reflect'}
+        if ts.ignore_index is not None:
+            mean = ts.sums[:, 0, :].sum(0) / float(len(ts) * ts.tile * ts.tile)
+            kw = {'border': 'constant', 'mask_fill': ts.ignore_index, 'fill': np.rint(mean)}
+        for k in range(len(self)):
+            lo = ts.start + k * bs
+            hi = min(lo + bs, ts.end)
+            mats, luts = batch_augment_params(self.rs, hi - lo, (ts.tile, ts.tile), self.out_hw, ch=ts.ch, **self.augment)
+            if ts.keep == 'device':
+                s_img, s_mask, src = img, mask, np.arange(lo, hi)
+            else:
+                s_img = img[lo:hi].to(self.device, non_blocking=True)
+                s_mask = mask[lo:hi].to(self.device, non_blocking=True) if mask is not None else None
+                src = np.arange(hi - lo)
+            x, y, _ = augment_batch(s_img, s_mask, src, mats, luts, self.out_hw, **kw)
+            yield x, y
+
+
 class TileSet:
     """Tiles of one size with their integer statistics, resident on the device (keep='device') or in pinned host memory (keep='host');
     the statistics always end on the host (numpy int64).  add() appends extract_photo's output, from_arrays() takes tiles cut elsewhere
@@ -591,10 +804,19 @@ class TileSet:
         view._lo, view._hi = self._lo + lo * span, self._lo + hi * span
         return view
 
-    def batches(self, batch_size, drop_last=True):
+    def batches(self, batch_size, drop_last=True, augment=None, seed=0, out=None, device='cuda'):
         """A re-iterable of (img uint8 [B,C,t,t], mask uint8 [B,t,t] or None): device tensors gathered by index (keep='device', what
-        Model.train takes as is), or host arrays out of the pinned store (keep='host', what data.TileFeeder takes)."""
-        return _Batches(self, batch_size, drop_last)
+        Model.train takes as is), or host arrays out of the pinned store (keep='host', what data.TileFeeder takes).
+
+        augment: a dict of batch_augment_params' keywords (scale, rotate, flip, vflip, brightness, contrast, gamma; {} for its defaults).
+        Every batch is then drawn anew and made by one launch of pylc_batch_augment, and the iterable yields DEVICE (img, mask) of size
+        `out` ((oh, ow) or one side; default: the tile) -- a host set uploads the batch's tiles to `device` first.  With an ignore_index
+        the border is constant: pixels the map takes outside the tile get that label and the image there is rint(the set's px mean);
+        without one the tile is mirrored (BORDER_REFLECT_101).  One RandomState(seed) belongs to the iterable and advances across
+        epochs.  augment=None: the stored tiles as they are (seed, out and device are not used)."""
+        if augment is None:
+            return _Batches(self, batch_size, drop_last)
+        return _AugmentedBatches(self, batch_size, drop_last, augment, seed, out, device)
 
     def oversample(self, rates, chunk=64, device='cuda'):
         """Augmentor.oversample (utils/augment.py:184-239) without its shuffle: a NEW tile set of the same keep mode that holds, for every

@@ -216,6 +216,7 @@ SIGNATURES = {
     'pylc_extract_tiles': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'pylc_tile_stats': (_I, [_P, _LL, _I, _I, _P, _I, _I, _P, _P, _P]),
     'pylc_augment_tiles': (_I, [_P, _P, _LL, _I, _I, _P, _P, _P, _LL, _I, _P, _P, _I, _P, _P, _P]),
+    'pylc_batch_augment': (_I, [_P, _P, _P, _LL, _I, _I, _I, _P, _P, _P, _LL, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     'pylc_confusion_matrix': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _P]),
     'pylc_confusion_matrix_ex': (_I, [_P, _I, _P, _I, _LL, _I, _I, _P, _I, _P, _P]),
     'pylc_logits_score': (_I, [_P, _I, _P, _I, _LL, _I, _P, _P, _P]),
