@@ -449,35 +449,79 @@ extern "C" size_t pylc_multiloss_workspace_floats(long long N, int C) {
     return (size_t)kLossBlocks * (3 + 3 * (size_t)C);
 }
 
-static int multiloss_stats_impl(const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N, int C, long long ignore,
-                                const float* cw, const float* pw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
-    hipStream_t st = as_stream(stream);
-    const int blocks = (int)(cdiv<long long>(N, 256) < kLossBlocks ? cdiv<long long>(N, 256) : kLossBlocks);
-#define LAUNCH_STATS_T(CC, TT, IGN, PW)                                                                                                                 \
+// ---- the launchers: one per kernel family (hard / soft targets) and direction, the runtime variant chosen inside -----------------------------
+template <int CC>
+static void stats_launch(int blocks, hipStream_t st, const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N,
+                         long long ignore, const float* cw, const float* pw, float* workspace, unsigned long long* n_bad) {
+#define STATS_K(TT, IGN, PW)                                                                                                                            \
     hipLaunchKernelGGL((multiloss_stats_kernel<CC, TT, IGN, PW>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
                        workspace, ignore, n_bad, pw)
-    if (!ign) {
-#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, false, false)
-        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
-#undef LAUNCH_STATS
-    } else if (pw != nullptr && target_bytes == 8) {
-#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, true, true)
-        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
-#undef LAUNCH_STATS
-    } else if (pw != nullptr) {
-#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, unsigned char, true, true)
-        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
-#undef LAUNCH_STATS
-    } else if (target_bytes == 8) {
-#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, long long, true, false)
-        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
-#undef LAUNCH_STATS
-    } else {
-#define LAUNCH_STATS(CC) LAUNCH_STATS_T(CC, unsigned char, true, false)
-        PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
-#undef LAUNCH_STATS
-    }
-#undef LAUNCH_STATS_T
+    if (!ign) STATS_K(long long, false, false);
+    else if (pw != nullptr && target_bytes == 8) STATS_K(long long, true, true);
+    else if (pw != nullptr) STATS_K(unsigned char, true, true);
+    else if (target_bytes == 8) STATS_K(long long, true, false);
+    else STATS_K(unsigned char, true, false);
+#undef STATS_K
+}
+
+template <int CC>
+static void stats_soft_launch(int blocks, hipStream_t st, const float* logits, int pitch, const SoftSrc& src, int kind, int target_bytes, long long N,
+                              const float* cw, const float* pw, float* workspace, unsigned long long* n_bad) {
+#define STATS_K(SRC, TT) \
+    hipLaunchKernelGGL((multiloss_stats_soft_kernel<CC, SRC, TT>), dim3(blocks), dim3(256), 0, st, logits, pitch, src, N, cw, pw, workspace, n_bad)
+    if (kind == kSoftProbs) STATS_K(kSoftProbs, float);
+    else if (kind == kSoftLogits) STATS_K(kSoftLogits, float);
+    else if (target_bytes == 8) STATS_K(kSoftSmooth, long long);
+    else STATS_K(kSoftSmooth, unsigned char);
+#undef STATS_K
+}
+
+// what the two backward families share: the cleared range word, the grid and how a row of dlogits is stored
+struct BwdGeom {
+    int blocks, Cstore, zero16;
+};
+
+static int bwd_geom(long long N, int C, const float* dlogits, int dpitch, unsigned int* amax_bits, hipStream_t st, BwdGeom& g) {
+    if (amax_bits != nullptr) PYLC_HIP(hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st));
+    g.blocks = (int)(cdiv<long long>(N, 256) < 4096 ? cdiv<long long>(N, 256) : 4096);
+    g.Cstore = ((C + 3) & ~3) <= dpitch ? ((C + 3) & ~3) : C;
+    g.zero16 = dpitch % 4 == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;      // then Cstore = roundup4(C) <= dpitch
+    return PYLC_OK;
+}
+
+template <int CC>
+static void bwd_launch(const BwdGeom& g, hipStream_t st, const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N,
+                       long long ignore, const float* cw, const float* pw, const float* stats, float inv_n, float w_ce, float w_dice, float w_focal,
+                       const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits) {
+#define BWD_K(TT, IGN, PW)                                                                                                                             \
+    hipLaunchKernelGGL((multiloss_bwd_kernel<CC, TT, IGN, PW>), dim3(g.blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
+                       stats, inv_n, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, g.Cstore, amax_bits, ignore, g.zero16, pw)
+    if (!ign) BWD_K(long long, false, false);
+    else if (pw != nullptr && target_bytes == 8) BWD_K(long long, true, true);
+    else if (pw != nullptr) BWD_K(unsigned char, true, true);
+    else if (target_bytes == 8) BWD_K(long long, true, false);
+    else BWD_K(unsigned char, true, false);
+#undef BWD_K
+}
+
+template <int CC>
+static void bwd_soft_launch(const BwdGeom& g, hipStream_t st, const float* logits, int pitch, const SoftSrc& src, int kind, int target_bytes,
+                            long long N, const float* cw, const float* pw, const float* stats, float w_ce, float w_dice, float w_focal,
+                            const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits) {
+#define BWD_K(SRC, TT)                                                                                                                        \
+    hipLaunchKernelGGL((multiloss_bwd_soft_kernel<CC, SRC, TT>), dim3(g.blocks), dim3(256), 0, st, logits, pitch, src, N, cw, pw, stats, w_ce, \
+                       w_dice, w_focal, grad_scale, dlogits, dpitch, g.Cstore, amax_bits, g.zero16)
+    if (kind == kSoftProbs) BWD_K(kSoftProbs, float);
+    else if (kind == kSoftLogits) BWD_K(kSoftLogits, float);
+    else if (target_bytes == 8) BWD_K(kSoftSmooth, long long);
+    else BWD_K(kSoftSmooth, unsigned char);
+#undef BWD_K
+}
+
+static int stats_blocks(long long N) { return (int)(cdiv<long long>(N, 256) < kLossBlocks ? cdiv<long long>(N, 256) : kLossBlocks); }
+
+// after the statistics kernel of either family: its launch check, then the per-block rows of the workspace summed into stats
+static int stats_finish(const float* workspace, int blocks, int C, float* stats, hipStream_t st) {
     PYLC_LAUNCH_CHECK();
     const int K = 3 + 3 * C;
     hipLaunchKernelGGL(column_sum_kernel, dim3(cdiv(K, 8)), dim3(256), 0, st, workspace, blocks, K, stats);
@@ -485,6 +529,122 @@ static int multiloss_stats_impl(const float* logits, int pitch, const void* targ
     return PYLC_OK;
 }
 
+static int multiloss_stats_impl(const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N, int C, long long ignore,
+                                const float* cw, const float* pw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
+    hipStream_t st = as_stream(stream);
+    const int blocks = stats_blocks(N);
+#define LAUNCH_STATS(CC) stats_launch<CC>(blocks, st, logits, pitch, target, target_bytes, ign, N, ignore, cw, pw, workspace, n_bad)
+    PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
+#undef LAUNCH_STATS
+    return stats_finish(workspace, blocks, C, stats, st);
+}
+
+static int multiloss_stats_soft_impl(const float* logits, int pitch, const SoftSrc& src, int kind, int target_bytes, long long N, int C,
+                                     const float* cw, const float* pw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
+    hipStream_t st = as_stream(stream);
+    const int blocks = stats_blocks(N);
+#define LAUNCH_STATS(CC) stats_soft_launch<CC>(blocks, st, logits, pitch, src, kind, target_bytes, N, cw, pw, workspace, n_bad)
+    PYLC_FOR_CLASSES(C, LAUNCH_STATS, "multiloss")
+#undef LAUNCH_STATS
+    return stats_finish(workspace, blocks, C, stats, st);
+}
+
+static int multiloss_bwd_impl(const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N, int C, long long ignore,
+                              const float* cw, const float* pw, const float* stats, double n_global, float w_ce, float w_dice, float w_focal,
+                              const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    hipStream_t st = as_stream(stream);
+    BwdGeom g;
+    if (int rc = bwd_geom(N, C, dlogits, dpitch, amax_bits, st, g)) return rc;
+    const float inv_n = ign ? 0.f : (float)(1.0 / n_global);
+#define LAUNCH_BWD(CC)                                                                                                                          \
+    bwd_launch<CC>(g, st, logits, pitch, target, target_bytes, ign, N, ignore, cw, pw, stats, inv_n, w_ce, w_dice, w_focal, grad_scale, dlogits, \
+                   dpitch, amax_bits)
+    PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
+#undef LAUNCH_BWD
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+static int multiloss_bwd_soft_impl(const float* logits, int pitch, const SoftSrc& src, int kind, int target_bytes, long long N, int C,
+                                   const float* cw, const float* pw, const float* stats, float w_ce, float w_dice, float w_focal,
+                                   const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
+    hipStream_t st = as_stream(stream);
+    BwdGeom g;
+    if (int rc = bwd_geom(N, C, dlogits, dpitch, amax_bits, st, g)) return rc;
+#define LAUNCH_BWD(CC)                                                                                                                           \
+    bwd_soft_launch<CC>(g, st, logits, pitch, src, kind, target_bytes, N, cw, pw, stats, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, \
+                        amax_bits)
+    PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
+#undef LAUNCH_BWD
+    PYLC_LAUNCH_CHECK();
+    return PYLC_OK;
+}
+
+// ---- the argument rules of the _ex, _w, _ls and _soft entry points, in the order each of them states them; `who` names the entry point ------
+static bool loss_aligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
+
+// a hard target: class count, smoothing (0 where the entry point has none), element size, pointer
+static int hard_target_check(const char* who, int C, float smoothing, const void* target, int target_bytes) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "%s: n_classes=%d unsupported (2..%d)", who, C, MAXC);
+    PYLC_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "%s: smoothing=%g outside [0, 1)", who, (double)smoothing);
+    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "%s: target_bytes=%d (1: uint8, 8: int64)", who, target_bytes);
+    PYLC_REQUIRE(target, "%s: target is NULL", who);
+    return PYLC_OK;
+}
+
+// a soft volume: class count, kind, temperature, pointer, extents and strides
+static int soft_volume_check(const char* who, int C, int kind, float inv_T, const float* soft, int H, int W, long long N, long long stride_b,
+                             long long stride_c, long long stride_h, long long stride_w) {
+    PYLC_REQUIRE(C >= 2 && C <= MAXC, "%s: n_classes=%d unsupported (2..%d)", who, C, MAXC);
+    PYLC_REQUIRE(kind == kSoftProbs || kind == kSoftLogits, "%s: kind=%d (0: probabilities, 1: teacher logits)", who, kind);
+    PYLC_REQUIRE(inv_T > 0.f && inv_T <= FLT_MAX, "%s: inv_T=%g is not a positive finite number", who, (double)inv_T);
+    PYLC_REQUIRE(soft, "%s: soft is NULL", who);
+    PYLC_REQUIRE(H > 0 && W > 0, "%s: H=%d or W=%d is not positive", who, H, W);
+    PYLC_REQUIRE(N > 0 && N % ((long long)H * W) == 0, "%s: N=%lld is not a positive multiple of H*W=%lld", who, N, (long long)H * W);
+    PYLC_REQUIRE(stride_b >= 0 && stride_c >= 0 && stride_h >= 0 && stride_w >= 0, "%s: a stride is negative (%lld, %lld, %lld, %lld)", who,
+                 stride_b, stride_c, stride_h, stride_w);
+    return PYLC_OK;
+}
+
+// the statistics side.  hard: `target` holds labels of target_bytes each, whose rules come first; otherwise it is a float volume
+// (target_bytes 4) that soft_volume_check has passed
+static int stats_check(const char* who, bool hard, float smoothing, const float* logits, int pitch, const void* target, int target_bytes,
+                       long long N, int C, const float* pw, const float* stats, const float* workspace, const unsigned long long* n_bad) {
+    if (int rc = hard ? hard_target_check(who, C, smoothing, target, target_bytes) : PYLC_OK) return rc;
+    PYLC_REQUIRE(pitch >= C, "%s: pitch=%d below n_classes=%d", who, pitch, C);
+    PYLC_REQUIRE(N > 0, "%s: N=%lld is not positive", who, N);
+    PYLC_REQUIRE(logits && stats && workspace, "%s: logits, stats or workspace is NULL", who);
+    PYLC_REQUIRE(loss_aligned(target, target_bytes) && loss_aligned(n_bad, 8) && loss_aligned(pw, 4), "%s: a buffer is not aligned to its element",
+                 who);
+    return PYLC_OK;
+}
+
+// the backward side, likewise; all of it comes before amax_bits is cleared
+static int bwd_check(const char* who, bool hard, float smoothing, const float* logits, int pitch, const void* target, int target_bytes,
+                     long long N, int C, const float* pw, const float* stats, const float* dlogits, int dpitch) {
+    if (int rc = hard ? hard_target_check(who, C, smoothing, target, target_bytes) : PYLC_OK) return rc;
+    PYLC_REQUIRE(pitch >= C && dpitch >= C, "%s: pitch=%d or dpitch=%d below n_classes=%d", who, pitch, dpitch, C);
+    PYLC_REQUIRE(N > 0, "%s: N=%lld is not positive", who, N);
+    PYLC_REQUIRE(logits && stats && dlogits, "%s: logits, stats or dlogits is NULL", who);
+    if (!hard) PYLC_REQUIRE(loss_aligned(target, 4) && loss_aligned(pw, 4), "%s: a buffer is not aligned to its element", who);
+    PYLC_REQUIRE(loss_aligned(target, target_bytes), "%s: an int64 target is not 8-byte aligned", who);
+    PYLC_REQUIRE(loss_aligned(pw, 4), "%s: pixel_weights is not 4-byte aligned", who);
+    return PYLC_OK;
+}
+
+static SoftSrc soft_volume(const float* soft, long long sb, long long sc, long long sh, long long sw, long long N, int H, int W, float inv_T) {
+    SoftSrc s{};
+    s.ptr = soft, s.sb = sb, s.sc = sc, s.sh = sh, s.sw = sw, s.HW = (long long)H * W, s.W = W, s.small = N < (1ll << 32), s.par = inv_T;
+    return s;
+}
+
+static SoftSrc soft_smooth(const void* target, float smoothing, long long ignore) {
+    SoftSrc s{};
+    s.ptr = target, s.par = smoothing, s.ignore = ignore, s.HW = 1, s.W = 1;
+    return s;
+}
+
+// ---- the entry points ---------------------------------------------------------------------------------------------------------------------
 extern "C" int pylc_multiloss_stats(const float* logits, int pitch, const int64_t* target, long long N, int C, const float* cw, float* stats,
                                     float* workspace, void* stream) {
     PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats: n_classes=%d unsupported (2..%d)", C, MAXC);
@@ -494,14 +654,7 @@ extern "C" int pylc_multiloss_stats(const float* logits, int pitch, const int64_
 
 extern "C" int pylc_multiloss_stats_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
                                        const float* cw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
-    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats_ex: n_classes=%d unsupported (2..%d)", C, MAXC);
-    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_stats_ex: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
-    PYLC_REQUIRE(target, "multiloss_stats_ex: target is NULL");
-    PYLC_REQUIRE(pitch >= C, "multiloss_stats_ex: pitch=%d below n_classes=%d", pitch, C);
-    PYLC_REQUIRE(N > 0, "multiloss_stats_ex: N=%lld is not positive", N);
-    PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_ex: logits, stats or workspace is NULL");
-    PYLC_REQUIRE((target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0) && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0,
-                 "multiloss_stats_ex: a buffer is not aligned to its element");
+    if (int rc = stats_check("multiloss_stats_ex", true, 0.f, logits, pitch, target, target_bytes, N, C, nullptr, stats, workspace, n_bad)) return rc;
     return multiloss_stats_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, nullptr, stats, workspace, n_bad, stream);
 }
 
@@ -509,15 +662,8 @@ extern "C" int pylc_multiloss_stats_ex(const float* logits, int pitch, const voi
 extern "C" int pylc_multiloss_stats_w(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
                                       const float* cw, const float* pixel_weights, float* stats, float* workspace, unsigned long long* n_bad,
                                       void* stream) {
-    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats_w: n_classes=%d unsupported (2..%d)", C, MAXC);
-    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_stats_w: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
-    PYLC_REQUIRE(target, "multiloss_stats_w: target is NULL");
-    PYLC_REQUIRE(pitch >= C, "multiloss_stats_w: pitch=%d below n_classes=%d", pitch, C);
-    PYLC_REQUIRE(N > 0, "multiloss_stats_w: N=%lld is not positive", N);
-    PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_w: logits, stats or workspace is NULL");
-    PYLC_REQUIRE((target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0) && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0 &&
-                     (reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0,
-                 "multiloss_stats_w: a buffer is not aligned to its element");
+    if (int rc = stats_check("multiloss_stats_w", true, 0.f, logits, pitch, target, target_bytes, N, C, pixel_weights, stats, workspace, n_bad))
+        return rc;
     return multiloss_stats_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, pixel_weights, stats, workspace, n_bad,
                                 stream);
 }
@@ -538,44 +684,6 @@ extern "C" int pylc_multiloss_finalize_ex(const float* stats, int C, float w_ce,
     return PYLC_OK;
 }
 
-static int multiloss_bwd_impl(const float* logits, int pitch, const void* target, int target_bytes, bool ign, long long N, int C, long long ignore,
-                              const float* cw, const float* pw, const float* stats, double n_global, float w_ce, float w_dice, float w_focal,
-                              const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
-    hipStream_t st = as_stream(stream);
-    if (amax_bits != nullptr) PYLC_HIP(hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st));
-    const int blocks = (int)(cdiv<long long>(N, 256) < 4096 ? cdiv<long long>(N, 256) : 4096);
-    const int Cstore = ((C + 3) & ~3) <= dpitch ? ((C + 3) & ~3) : C;
-    const float inv_n = ign ? 0.f : (float)(1.0 / n_global);
-    const int zero16 = dpitch % 4 == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;      // then Cstore = roundup4(C) <= dpitch
-#define LAUNCH_BWD_T(CC, TT, IGN, PW)                                                                                                                 \
-    hipLaunchKernelGGL((multiloss_bwd_kernel<CC, TT, IGN, PW>), dim3(blocks), dim3(256), 0, st, logits, pitch, static_cast<const TT*>(target), N, cw, \
-                       stats, inv_n, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, Cstore, amax_bits, ignore, zero16, pw)
-    if (!ign) {
-#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, false, false)
-        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
-#undef LAUNCH_BWD
-    } else if (pw != nullptr && target_bytes == 8) {
-#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, true, true)
-        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
-#undef LAUNCH_BWD
-    } else if (pw != nullptr) {
-#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, unsigned char, true, true)
-        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
-#undef LAUNCH_BWD
-    } else if (target_bytes == 8) {
-#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, long long, true, false)
-        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
-#undef LAUNCH_BWD
-    } else {
-#define LAUNCH_BWD(CC) LAUNCH_BWD_T(CC, unsigned char, true, false)
-        PYLC_FOR_CLASSES(C, LAUNCH_BWD, "multiloss")
-#undef LAUNCH_BWD
-    }
-#undef LAUNCH_BWD_T
-    PYLC_LAUNCH_CHECK();
-    return PYLC_OK;
-}
-
 extern "C" int pylc_multiloss_bwd(const float* logits, int pitch, const int64_t* target, long long N, int C, const float* cw,
                                   const float* stats, double n_global, float w_ce, float w_dice, float w_focal, const float* grad_scale,
                                   float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
@@ -588,13 +696,7 @@ extern "C" int pylc_multiloss_bwd(const float* logits, int pitch, const int64_t*
 extern "C" int pylc_multiloss_bwd_ex(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
                                      const float* cw, const float* stats, float w_ce, float w_dice, float w_focal, const float* grad_scale,
                                      float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
-    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd_ex: n_classes=%d unsupported (2..%d)", C, MAXC);   // before amax_bits is cleared
-    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_bwd_ex: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
-    PYLC_REQUIRE(target, "multiloss_bwd_ex: target is NULL");
-    PYLC_REQUIRE(pitch >= C && dpitch >= C, "multiloss_bwd_ex: pitch=%d or dpitch=%d below n_classes=%d", pitch, dpitch, C);
-    PYLC_REQUIRE(N > 0, "multiloss_bwd_ex: N=%lld is not positive", N);
-    PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_ex: logits, stats or dlogits is NULL");
-    PYLC_REQUIRE(target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0, "multiloss_bwd_ex: an int64 target is not 8-byte aligned");
+    if (int rc = bwd_check("multiloss_bwd_ex", true, 0.f, logits, pitch, target, target_bytes, N, C, nullptr, stats, dlogits, dpitch)) return rc;
     return multiloss_bwd_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, nullptr, stats, 1.0, w_ce, w_dice, w_focal,
                               grad_scale, dlogits, dpitch, amax_bits, stream);
 }
@@ -602,116 +704,17 @@ extern "C" int pylc_multiloss_bwd_ex(const float* logits, int pitch, const void*
 extern "C" int pylc_multiloss_bwd_w(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
                                     const float* cw, const float* pixel_weights, const float* stats, float w_ce, float w_dice, float w_focal,
                                     const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
-    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd_w: n_classes=%d unsupported (2..%d)", C, MAXC);    // before amax_bits is cleared
-    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_bwd_w: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
-    PYLC_REQUIRE(target, "multiloss_bwd_w: target is NULL");
-    PYLC_REQUIRE(pitch >= C && dpitch >= C, "multiloss_bwd_w: pitch=%d or dpitch=%d below n_classes=%d", pitch, dpitch, C);
-    PYLC_REQUIRE(N > 0, "multiloss_bwd_w: N=%lld is not positive", N);
-    PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_w: logits, stats or dlogits is NULL");
-    PYLC_REQUIRE(target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0, "multiloss_bwd_w: an int64 target is not 8-byte aligned");
-    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0, "multiloss_bwd_w: pixel_weights is not 4-byte aligned");
+    if (int rc = bwd_check("multiloss_bwd_w", true, 0.f, logits, pitch, target, target_bytes, N, C, pixel_weights, stats, dlogits, dpitch)) return rc;
     return multiloss_bwd_impl(logits, pitch, target, target_bytes, true, N, C, (long long)ignore_index, cw, pixel_weights, stats, 1.0, w_ce, w_dice,
                               w_focal, grad_scale, dlogits, dpitch, amax_bits, stream);
-}
-
-// ---- soft targets: the host side -----------------------------------------------------------------------------------------------------------
-static int multiloss_stats_soft_impl(const float* logits, int pitch, const SoftSrc& src, int kind, int target_bytes, long long N, int C,
-                                     const float* cw, const float* pw, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
-    hipStream_t st = as_stream(stream);
-    const int blocks = (int)(cdiv<long long>(N, 256) < kLossBlocks ? cdiv<long long>(N, 256) : kLossBlocks);
-#define LAUNCH_SOFT_T(CC, SRC, TT)                                                                                                          \
-    hipLaunchKernelGGL((multiloss_stats_soft_kernel<CC, SRC, TT>), dim3(blocks), dim3(256), 0, st, logits, pitch, src, N, cw, pw, workspace, \
-                       n_bad)
-    if (kind == kSoftProbs) {
-#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftProbs, float)
-        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
-#undef LAUNCH_SOFT
-    } else if (kind == kSoftLogits) {
-#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftLogits, float)
-        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
-#undef LAUNCH_SOFT
-    } else if (target_bytes == 8) {
-#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftSmooth, long long)
-        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
-#undef LAUNCH_SOFT
-    } else {
-#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftSmooth, unsigned char)
-        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
-#undef LAUNCH_SOFT
-    }
-#undef LAUNCH_SOFT_T
-    PYLC_LAUNCH_CHECK();
-    const int K = 3 + 3 * C;
-    hipLaunchKernelGGL(column_sum_kernel, dim3(cdiv(K, 8)), dim3(256), 0, st, workspace, blocks, K, stats);
-    PYLC_LAUNCH_CHECK();
-    return PYLC_OK;
-}
-
-static int multiloss_bwd_soft_impl(const float* logits, int pitch, const SoftSrc& src, int kind, int target_bytes, long long N, int C,
-                                   const float* cw, const float* pw, const float* stats, float w_ce, float w_dice, float w_focal,
-                                   const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
-    hipStream_t st = as_stream(stream);
-    if (amax_bits != nullptr) PYLC_HIP(hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st));
-    const int blocks = (int)(cdiv<long long>(N, 256) < 4096 ? cdiv<long long>(N, 256) : 4096);
-    const int Cstore = ((C + 3) & ~3) <= dpitch ? ((C + 3) & ~3) : C;
-    const int zero16 = dpitch % 4 == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0;
-#define LAUNCH_SOFT_T(CC, SRC, TT)                                                                                                       \
-    hipLaunchKernelGGL((multiloss_bwd_soft_kernel<CC, SRC, TT>), dim3(blocks), dim3(256), 0, st, logits, pitch, src, N, cw, pw, stats, w_ce, \
-                       w_dice, w_focal, grad_scale, dlogits, dpitch, Cstore, amax_bits, zero16)
-    if (kind == kSoftProbs) {
-#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftProbs, float)
-        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
-#undef LAUNCH_SOFT
-    } else if (kind == kSoftLogits) {
-#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftLogits, float)
-        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
-#undef LAUNCH_SOFT
-    } else if (target_bytes == 8) {
-#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftSmooth, long long)
-        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
-#undef LAUNCH_SOFT
-    } else {
-#define LAUNCH_SOFT(CC) LAUNCH_SOFT_T(CC, kSoftSmooth, unsigned char)
-        PYLC_FOR_CLASSES(C, LAUNCH_SOFT, "multiloss")
-#undef LAUNCH_SOFT
-    }
-#undef LAUNCH_SOFT_T
-    PYLC_LAUNCH_CHECK();
-    return PYLC_OK;
-}
-
-// the argument rules the four entry points share; `who` is a string literal
-#define PYLC_SOFT_VOLUME_ARGS(who)                                                                                                        \
-    PYLC_REQUIRE(C >= 2 && C <= MAXC, who ": n_classes=%d unsupported (2..%d)", C, MAXC);                                                  \
-    PYLC_REQUIRE(kind == kSoftProbs || kind == kSoftLogits, who ": kind=%d (0: probabilities, 1: teacher logits)", kind);                  \
-    PYLC_REQUIRE(inv_T > 0.f && inv_T <= FLT_MAX, who ": inv_T=%g is not a positive finite number", (double)inv_T);                        \
-    PYLC_REQUIRE(soft, who ": soft is NULL");                                                                                              \
-    PYLC_REQUIRE(H > 0 && W > 0, who ": H=%d or W=%d is not positive", H, W);                                                              \
-    PYLC_REQUIRE(N > 0 && N % ((long long)H * W) == 0, who ": N=%lld is not a positive multiple of H*W=%lld", N, (long long)H * W);        \
-    PYLC_REQUIRE(stride_b >= 0 && stride_c >= 0 && stride_h >= 0 && stride_w >= 0, who ": a stride is negative (%lld, %lld, %lld, %lld)",  \
-                 stride_b, stride_c, stride_h, stride_w)
-
-static SoftSrc soft_volume(const float* soft, long long sb, long long sc, long long sh, long long sw, long long N, int H, int W, float inv_T) {
-    SoftSrc s{};
-    s.ptr = soft, s.sb = sb, s.sc = sc, s.sh = sh, s.sw = sw, s.HW = (long long)H * W, s.W = W, s.small = N < (1ll << 32), s.par = inv_T;
-    return s;
-}
-
-static SoftSrc soft_smooth(const void* target, float smoothing, long long ignore) {
-    SoftSrc s{};
-    s.ptr = target, s.par = smoothing, s.ignore = ignore, s.HW = 1, s.W = 1;
-    return s;
 }
 
 extern "C" int pylc_multiloss_stats_soft(const float* logits, int pitch, long long N, int H, int W, int C, const float* soft, long long stride_b,
                                          long long stride_c, long long stride_h, long long stride_w, int kind, float inv_T, const float* cw,
                                          const float* pixel_weights, float* stats, float* workspace, unsigned long long* n_bad, void* stream) {
-    PYLC_SOFT_VOLUME_ARGS("multiloss_stats_soft");
-    PYLC_REQUIRE(pitch >= C, "multiloss_stats_soft: pitch=%d below n_classes=%d", pitch, C);
-    PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_soft: logits, stats or workspace is NULL");
-    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(soft) & 3) == 0 && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0 &&
-                     (reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0,
-                 "multiloss_stats_soft: a buffer is not aligned to its element");
+    const char* who = "multiloss_stats_soft";
+    if (int rc = soft_volume_check(who, C, kind, inv_T, soft, H, W, N, stride_b, stride_c, stride_h, stride_w)) return rc;
+    if (int rc = stats_check(who, false, 0.f, logits, pitch, soft, 4, N, C, pixel_weights, stats, workspace, n_bad)) return rc;
     return multiloss_stats_soft_impl(logits, pitch, soft_volume(soft, stride_b, stride_c, stride_h, stride_w, N, H, W, inv_T), kind, 4, N, C, cw,
                                      pixel_weights, stats, workspace, n_bad, stream);
 }
@@ -720,11 +723,9 @@ extern "C" int pylc_multiloss_bwd_soft(const float* logits, int pitch, long long
                                        long long stride_c, long long stride_h, long long stride_w, int kind, float inv_T, const float* cw,
                                        const float* pixel_weights, const float* stats, float w_ce, float w_dice, float w_focal,
                                        const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
-    PYLC_SOFT_VOLUME_ARGS("multiloss_bwd_soft");                                                          // before amax_bits is cleared
-    PYLC_REQUIRE(pitch >= C && dpitch >= C, "multiloss_bwd_soft: pitch=%d or dpitch=%d below n_classes=%d", pitch, dpitch, C);
-    PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_soft: logits, stats or dlogits is NULL");
-    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(soft) & 3) == 0 && (reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0,
-                 "multiloss_bwd_soft: a buffer is not aligned to its element");
+    const char* who = "multiloss_bwd_soft";
+    if (int rc = soft_volume_check(who, C, kind, inv_T, soft, H, W, N, stride_b, stride_c, stride_h, stride_w)) return rc;
+    if (int rc = bwd_check(who, false, 0.f, logits, pitch, soft, 4, N, C, pixel_weights, stats, dlogits, dpitch)) return rc;
     return multiloss_bwd_soft_impl(logits, pitch, soft_volume(soft, stride_b, stride_c, stride_h, stride_w, N, H, W, inv_T), kind, 4, N, C, cw,
                                    pixel_weights, stats, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, amax_bits, stream);
 }
@@ -732,16 +733,8 @@ extern "C" int pylc_multiloss_bwd_soft(const float* logits, int pitch, long long
 extern "C" int pylc_multiloss_stats_ls(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
                                        const float* cw, const float* pixel_weights, float smoothing, float* stats, float* workspace,
                                        unsigned long long* n_bad, void* stream) {
-    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_stats_ls: n_classes=%d unsupported (2..%d)", C, MAXC);
-    PYLC_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "multiloss_stats_ls: smoothing=%g outside [0, 1)", (double)smoothing);
-    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_stats_ls: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
-    PYLC_REQUIRE(target, "multiloss_stats_ls: target is NULL");
-    PYLC_REQUIRE(pitch >= C, "multiloss_stats_ls: pitch=%d below n_classes=%d", pitch, C);
-    PYLC_REQUIRE(N > 0, "multiloss_stats_ls: N=%lld is not positive", N);
-    PYLC_REQUIRE(logits && stats && workspace, "multiloss_stats_ls: logits, stats or workspace is NULL");
-    PYLC_REQUIRE((target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0) && (reinterpret_cast<uintptr_t>(n_bad) & 7) == 0 &&
-                     (reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0,
-                 "multiloss_stats_ls: a buffer is not aligned to its element");
+    if (int rc = stats_check("multiloss_stats_ls", true, smoothing, logits, pitch, target, target_bytes, N, C, pixel_weights, stats, workspace, n_bad))
+        return rc;
     return multiloss_stats_soft_impl(logits, pitch, soft_smooth(target, smoothing, (long long)ignore_index), kSoftSmooth, target_bytes, N, C, cw,
                                      pixel_weights, stats, workspace, n_bad, stream);
 }
@@ -749,15 +742,8 @@ extern "C" int pylc_multiloss_stats_ls(const float* logits, int pitch, const voi
 extern "C" int pylc_multiloss_bwd_ls(const float* logits, int pitch, const void* target, int target_bytes, long long N, int C, int ignore_index,
                                      const float* cw, const float* pixel_weights, float smoothing, const float* stats, float w_ce, float w_dice,
                                      float w_focal, const float* grad_scale, float* dlogits, int dpitch, unsigned int* amax_bits, void* stream) {
-    PYLC_REQUIRE(C >= 2 && C <= MAXC, "multiloss_bwd_ls: n_classes=%d unsupported (2..%d)", C, MAXC);   // before amax_bits is cleared
-    PYLC_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "multiloss_bwd_ls: smoothing=%g outside [0, 1)", (double)smoothing);
-    PYLC_REQUIRE(target_bytes == 1 || target_bytes == 8, "multiloss_bwd_ls: target_bytes=%d (1: uint8, 8: int64)", target_bytes);
-    PYLC_REQUIRE(target, "multiloss_bwd_ls: target is NULL");
-    PYLC_REQUIRE(pitch >= C && dpitch >= C, "multiloss_bwd_ls: pitch=%d or dpitch=%d below n_classes=%d", pitch, dpitch, C);
-    PYLC_REQUIRE(N > 0, "multiloss_bwd_ls: N=%lld is not positive", N);
-    PYLC_REQUIRE(logits && stats && dlogits, "multiloss_bwd_ls: logits, stats or dlogits is NULL");
-    PYLC_REQUIRE(target_bytes != 8 || (reinterpret_cast<uintptr_t>(target) & 7) == 0, "multiloss_bwd_ls: an int64 target is not 8-byte aligned");
-    PYLC_REQUIRE((reinterpret_cast<uintptr_t>(pixel_weights) & 3) == 0, "multiloss_bwd_ls: pixel_weights is not 4-byte aligned");
+    if (int rc = bwd_check("multiloss_bwd_ls", true, smoothing, logits, pitch, target, target_bytes, N, C, pixel_weights, stats, dlogits, dpitch))
+        return rc;
     return multiloss_bwd_soft_impl(logits, pitch, soft_smooth(target, smoothing, (long long)ignore_index), kSoftSmooth, target_bytes, N, C, cw,
                                    pixel_weights, stats, w_ce, w_dice, w_focal, grad_scale, dlogits, dpitch, amax_bits, stream);
 }

@@ -387,6 +387,14 @@ static void mine_nll_launch(bool vec, int blocks, hipStream_t st, const float* l
                            ign, pw, pw_vec, nll_out, out_vec, ghist, info);
 }
 
+template <int C, typename... Args>
+static void mine_nll_pick(bool hist, int target_bytes, Args... args) {
+    if (hist && target_bytes == 8) mine_nll_launch<C, long long, true>(args...);
+    else if (hist) mine_nll_launch<C, unsigned char, true>(args...);
+    else if (target_bytes == 8) mine_nll_launch<C, long long, false>(args...);
+    else mine_nll_launch<C, unsigned char, false>(args...);
+}
+
 }  // namespace pylc
 
 using namespace pylc;
@@ -434,25 +442,10 @@ static int mine_nll_dispatch(bool hist, const float* logits, int pitch, const vo
     const int blocks = mine_blocks(N);
     const long long ign = ignore_index;
     const int pw_vec = mine_al16(pw), out_vec = mine_al16(nll_out);
-#define LAUNCH_MN_T(CC, TT, HIST) mine_nll_launch<CC, TT, HIST>(vec, blocks, st, logits, pitch, target, N, ign, pw, pw_vec, nll_out, out_vec, ghist, info)
-    if (hist && target_bytes == 8) {
-#define LAUNCH_MN(CC) LAUNCH_MN_T(CC, long long, true)
-        PYLC_FOR_CLASSES(C, LAUNCH_MN, "mining")
+#define LAUNCH_MN(CC) \
+    mine_nll_pick<CC>(hist, target_bytes, vec, blocks, st, logits, pitch, target, N, ign, pw, pw_vec, nll_out, out_vec, ghist, info)
+    PYLC_FOR_CLASSES(C, LAUNCH_MN, "mining")
 #undef LAUNCH_MN
-    } else if (hist) {
-#define LAUNCH_MN(CC) LAUNCH_MN_T(CC, unsigned char, true)
-        PYLC_FOR_CLASSES(C, LAUNCH_MN, "mining")
-#undef LAUNCH_MN
-    } else if (target_bytes == 8) {
-#define LAUNCH_MN(CC) LAUNCH_MN_T(CC, long long, false)
-        PYLC_FOR_CLASSES(C, LAUNCH_MN, "mining")
-#undef LAUNCH_MN
-    } else {
-#define LAUNCH_MN(CC) LAUNCH_MN_T(CC, unsigned char, false)
-        PYLC_FOR_CLASSES(C, LAUNCH_MN, "mining")
-#undef LAUNCH_MN
-    }
-#undef LAUNCH_MN_T
     PYLC_LAUNCH_CHECK();
     return PYLC_OK;
 }

@@ -563,29 +563,74 @@ def _soft_strides(soft):
     return tuple(int(v) for v in soft.stride())
 
 
+def _check_labels(target, logits):
+    b, c, h, w = logits.shape
+    if target is None or target.dtype not in (torch.uint8, torch.int64) or tuple(target.shape) != (b, h, w):
+        raise L.PylcError('target must be uint8 or int64 [B,H,W] matching the logits')
+
+
 def multiloss_forward(needs, logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index=None, bad=None, pixel_weights=None,
                       soft_target=None, soft_kind='probs', temperature=1.0, label_smoothing=0.0):
-    """Saves (logits, target, stats, class_weights[, pixel_weights]); with a soft_target that tensor, as it came, is the saved target."""
+    """Saves (logits, target, stats, class_weights[, pixel_weights]); with a soft_target that tensor, as it came, is the saved target.
+    Each path states its argument rules and names its statistics entry point with the arguments between (logits, pitch) and the outputs;
+    the allocation, the exchange and the finalisation below them are one.  n_global stays None on every path but the plain one, whose
+    finalisation takes the pixel count from the host and which neither reads nor checks `bad`."""
     L.init()
     logits = as_nhwc(logits)
     b, c, h, w = logits.shape
     n = b * h * w
-    if soft_target is not None or label_smoothing != 0.0:
-        return _multiloss_forward_soft(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights,
-                                       soft_target, soft_kind, temperature, label_smoothing)
-    target = target.contiguous()
-    if pixel_weights is not None:
-        if (not torch.is_tensor(pixel_weights) or pixel_weights.dtype != torch.float32 or tuple(pixel_weights.shape) != (b, h, w)
-                or pixel_weights.device != logits.device):
-            raise L.PylcError('pixel_weights must be float32 [B,H,W] matching the logits, on their device')
-        pixel_weights = pixel_weights.detach().contiguous()
-        if ignore_index is None:
-            ignore_index = MultiLossFn.NO_IGNORE
-    if ignore_index is not None:
-        return _multiloss_forward_ignore(logits, target, class_weights, w_ce, w_dice, w_focal, group, int(ignore_index), bad, pixel_weights)
-    if target.dtype != torch.int64 or tuple(target.shape) != (b, h, w):
-        raise L.PylcError('target must be int64 [B,H,W] matching the logits')
     dev = logits.device
+    n_global = state_soft = None
+    if soft_target is not None or label_smoothing != 0.0:
+        eps = float(label_smoothing)
+        if not 0.0 <= eps < 1.0:
+            raise L.PylcError('label_smoothing must lie in [0, 1), got %r' % (label_smoothing,))
+        _check_bad(bad, logits)
+        if pixel_weights is not None:
+            pixel_weights = _check_pixel_weights(pixel_weights, logits)
+        if soft_target is not None:
+            if eps != 0.0:
+                raise L.PylcError('label_smoothing applies to hard targets: it cannot be combined with a soft_target')
+            if target is not None:
+                raise L.PylcError('pass target=None with a soft_target: the rows of the soft tensor are the target')
+            if ignore_index is not None:
+                raise L.PylcError('ignore_index has no meaning with a soft_target: a row that sums to 0 leaves its pixel out')
+            if soft_kind not in SOFT_KINDS:
+                raise L.PylcError("soft_kind is 'probs' or 'logits', got %r" % (soft_kind,))
+            inv_t = soft_inv_temperature(temperature)
+            if (not torch.is_tensor(soft_target) or soft_target.dtype != torch.float32 or tuple(soft_target.shape) != (b, c, h, w)
+                    or soft_target.device != dev):
+                raise L.PylcError('soft_target must be float32 [B,C,H,W] matching the logits, on their device')
+            target = soft_target.detach()                           # a view as it came: read through its strides, never copied
+            state_soft = (soft_kind, inv_t if soft_kind == 'logits' else 1.0)
+            stats_fn, mid = lib.pylc_multiloss_stats_soft, (n, h, w, c, ptr(target), *_soft_strides(target), SOFT_KINDS[soft_kind], state_soft[1],
+                                                            ptr(class_weights), ptr(pixel_weights))
+        else:
+            _check_labels(target, logits)
+            target = target.contiguous()
+            ignore_index = MultiLossFn.NO_IGNORE if ignore_index is None else int(ignore_index)
+            state_soft = ('smooth', eps)
+            stats_fn, mid = lib.pylc_multiloss_stats_ls, (ptr(target), target.element_size(), n, c, ignore_index, ptr(class_weights),
+                                                          ptr(pixel_weights), eps)
+    else:
+        target = target.contiguous()
+        if pixel_weights is not None:
+            pixel_weights = _check_pixel_weights(pixel_weights, logits)
+            if ignore_index is None:
+                ignore_index = MultiLossFn.NO_IGNORE
+        if ignore_index is not None:
+            ignore_index = int(ignore_index)
+            _check_labels(target, logits)
+            _check_bad(bad, logits)
+            stats_fn, mid = lib.pylc_multiloss_stats_ex, (ptr(target), target.element_size(), n, c, ignore_index, ptr(class_weights))
+            if pixel_weights is not None:
+                stats_fn, mid = lib.pylc_multiloss_stats_w, mid + (ptr(pixel_weights),)
+        else:
+            if target.dtype != torch.int64 or tuple(target.shape) != (b, h, w):
+                raise L.PylcError('target must be int64 [B,H,W] matching the logits')
+            n_global = float(n)
+            stats_fn, mid = lib.pylc_multiloss_stats, (ptr(target), n, c, ptr(class_weights))
+    plain = n_global is not None
     st = stream()
     k = 3 + 3 * c
     # data parallel: two more floats ride on the statistics message -- this rank's tile count b and b^2 -- so that unequal shards are
@@ -594,99 +639,21 @@ def multiloss_forward(needs, logits, target, class_weights, w_ce, w_dice, w_foca
     # in exactly the case it is meant to catch.
     stats = torch.empty(k + (2 if group is not None else 0), device=dev)
     ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
-    check(lib.pylc_multiloss_stats(ptr(logits), pitch_of(logits), ptr(target), n, c, ptr(class_weights), ptr(stats), ptr(ws), st))
-    n_global = float(n)
+    check(stats_fn(ptr(logits), pitch_of(logits), *mid, ptr(stats), ptr(ws), *(() if plain else (ptr(bad),)), st))
     if group is not None:
         stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
         _runtime.sync_all_reduce(stats, group)   # Dice / weighted CE are not shard-decomposable
-        n_global = float(n) * dist.get_world_size(group)
-        note_shard_pair(stats[k:], dist.get_world_size(group))
+        world = dist.get_world_size(group)
+        note_shard_pair(stats[k:], world)
+        if plain:
+            n_global *= world
     losses = torch.empty(4, device=dev)
-    check(lib.pylc_multiloss_finalize(ptr(stats), n_global, c, w_ce, w_dice, w_focal, ptr(losses), st))
-    return losses, (logits, target, stats, class_weights), LossState((n_global, w_ce, w_dice, w_focal, group)), ()
-
-
-def _multiloss_forward_ignore(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights=None):
-    b, c, h, w = logits.shape
-    n = b * h * w
-    if target.dtype not in (torch.uint8, torch.int64) or tuple(target.shape) != (b, h, w):
-        raise L.PylcError('target must be uint8 or int64 [B,H,W] matching the logits')
-    if bad is not None and (bad.dtype != torch.int64 or bad.numel() != 1 or bad.device != logits.device):
-        raise L.PylcError('bad must be an int64 [1] tensor on the device of the logits')
-    dev = logits.device
-    st = stream()
-    k = 3 + 3 * c
-    stats = torch.empty(k + (2 if group is not None else 0), device=dev)         # (the shard pair rides along as on the plain path)
-    ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
-    if pixel_weights is None:
-        check(lib.pylc_multiloss_stats_ex(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
-                                          ptr(class_weights), ptr(stats), ptr(ws), ptr(bad), st))
-    else:
-        check(lib.pylc_multiloss_stats_w(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
-                                         ptr(class_weights), ptr(pixel_weights), ptr(stats), ptr(ws), ptr(bad), st))
-    if group is not None:
-        stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
-        _runtime.sync_all_reduce(stats, group)
-        note_shard_pair(stats[k:], dist.get_world_size(group))
-    losses = torch.empty(4, device=dev)
-    check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))      # n_valid (sum u): from the reduced class counts
+    if plain:
+        check(lib.pylc_multiloss_finalize(ptr(stats), n_global, c, w_ce, w_dice, w_focal, ptr(losses), st))
+    else:                                                           # n_valid (sum u, sum u q): from the reduced class counts
+        check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))
     saved = (logits, target, stats, class_weights) + (() if pixel_weights is None else (pixel_weights,))
-    return losses, saved, LossState((None, w_ce, w_dice, w_focal, group), ignore_index), ()
-
-
-def _multiloss_forward_soft(logits, target, class_weights, w_ce, w_dice, w_focal, group, ignore_index, bad, pixel_weights, soft_target,
-                            soft_kind, temperature, label_smoothing):
-    """The soft-target paths of multiloss_forward: a volume or teacher logits (pylc_multiloss_stats_soft), or a smoothed hard target
-    (pylc_multiloss_stats_ls); the statistics exchange and the finalisation are those of _multiloss_forward_ignore."""
-    b, c, h, w = logits.shape
-    n = b * h * w
-    dev = logits.device
-    eps = float(label_smoothing)
-    if not 0.0 <= eps < 1.0:
-        raise L.PylcError('label_smoothing must lie in [0, 1), got %r' % (label_smoothing,))
-    _check_bad(bad, logits)
-    if pixel_weights is not None:
-        pixel_weights = _check_pixel_weights(pixel_weights, logits)
-    if soft_target is not None:
-        if eps != 0.0:
-            raise L.PylcError('label_smoothing applies to hard targets: it cannot be combined with a soft_target')
-        if target is not None:
-            raise L.PylcError('pass target=None with a soft_target: the rows of the soft tensor are the target')
-        if ignore_index is not None:
-            raise L.PylcError('ignore_index has no meaning with a soft_target: a row that sums to 0 leaves its pixel out')
-        if soft_kind not in SOFT_KINDS:
-            raise L.PylcError("soft_kind is 'probs' or 'logits', got %r" % (soft_kind,))
-        inv_t = soft_inv_temperature(temperature)
-        if (not torch.is_tensor(soft_target) or soft_target.dtype != torch.float32 or tuple(soft_target.shape) != (b, c, h, w)
-                or soft_target.device != dev):
-            raise L.PylcError('soft_target must be float32 [B,C,H,W] matching the logits, on their device')
-        soft_target = soft_target.detach()                      # a view as it came: read through its strides, never copied
-        state_soft = (soft_kind, inv_t if soft_kind == 'logits' else 1.0)
-    else:
-        if target is None or target.dtype not in (torch.uint8, torch.int64) or tuple(target.shape) != (b, h, w):
-            raise L.PylcError('target must be uint8 or int64 [B,H,W] matching the logits')
-        target = target.contiguous()
-        ignore_index = MultiLossFn.NO_IGNORE if ignore_index is None else int(ignore_index)
-        state_soft = ('smooth', eps)
-    st = stream()
-    k = 3 + 3 * c
-    stats = torch.empty(k + (2 if group is not None else 0), device=dev)         # (the shard pair rides along as on the plain path)
-    ws = torch.empty(lib.pylc_multiloss_workspace_floats(n, c), device=dev)
-    if soft_target is not None:
-        check(lib.pylc_multiloss_stats_soft(ptr(logits), pitch_of(logits), n, h, w, c, ptr(soft_target), *_soft_strides(soft_target),
-                                            SOFT_KINDS[soft_kind], state_soft[1], ptr(class_weights), ptr(pixel_weights), ptr(stats), ptr(ws),
-                                            ptr(bad), st))
-    else:
-        check(lib.pylc_multiloss_stats_ls(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, ignore_index,
-                                          ptr(class_weights), ptr(pixel_weights), eps, ptr(stats), ptr(ws), ptr(bad), st))
-    if group is not None:
-        stats[k:].copy_(_shard_pair(b, dev), non_blocking=True)
-        _runtime.sync_all_reduce(stats, group)
-        note_shard_pair(stats[k:], dist.get_world_size(group))
-    losses = torch.empty(4, device=dev)
-    check(lib.pylc_multiloss_finalize_ex(ptr(stats), c, w_ce, w_dice, w_focal, ptr(losses), st))      # sum u q: from the reduced class counts
-    saved = (logits, target if soft_target is None else soft_target, stats, class_weights) + (() if pixel_weights is None else (pixel_weights,))
-    return losses, saved, LossState((None, w_ce, w_dice, w_focal, group), ignore_index, state_soft), ()
+    return losses, saved, LossState((n_global, w_ce, w_dice, w_focal, group), ignore_index, state_soft), ()
 
 
 def multiloss_backward(state, saved, needs, dlosses):
@@ -702,7 +669,7 @@ def multiloss_backward(state, saved, needs, dlosses):
     dl = empty_nhwc(b, c, h, w, logits.device, cp)
     amax = torch.empty(1, dtype=torch.int32, device=logits.device) if ranges_needed() and _runtime.fused_grad_ranges else None
     ignore = state.ignore
-    soft = getattr(state, 'soft', None)
+    soft = state.soft
     if soft is not None and soft[0] == 'smooth':
         check(lib.pylc_multiloss_bwd_ls(ptr(logits), pitch_of(logits), ptr(target), target.element_size(), n, c, int(ignore), ptr(cw), ptr(pw),
                                         soft[1], ptr(stats), w_ce, w_dice, w_focal, ptr(gs), ptr(dl), cp, ptr(amax), stream()))
