@@ -263,7 +263,10 @@ int pylc_relu_bwd_bits(const float* dout, const void* mask, float* g_out, long l
 /* 0 when pylc_conv2d_dgrad(d, ...) only reads d->w_planes_t (w_crsk may then be NULL and the transpose be skipped). */
 int pylc_conv2d_dgrad_needs_f32_weights(const PylcConvDesc* d);
 /* dw (KRSC) = sum over pixels of dy (x) x.  workspace: pylc_conv2d_wgrad_workspace(d) bytes
- * (deterministic split-K slabs, reduced in a fixed order).  dbias (may be NULL) = sum_pixels dy. */
+ * (deterministic split-K slabs, reduced in a fixed order).  dbias (may be NULL) = sum_pixels dy.
+ * The workspace need not be initialised: every float of every slab is written before the sum reads it.
+ * An fp32 dy (dy_fmt = 0) is read up to channel roundup4(Cout) of each pixel (hence y_pitch >= roundup4(Cout)); channels
+ * [Cout, roundup4(Cout)) reach no row of dw, so they need not hold the zeros pylc_conv2d_fwd writes there. */
 size_t pylc_conv2d_wgrad_workspace(const PylcConvDesc* d);
 int pylc_conv2d_wgrad(const PylcConvDesc* d, const float* x, const float* dy, float* dw_krsc,
                       float* dbias /* must be NULL: take sums[0:C] of pylc_bn_stats(dy) */,
